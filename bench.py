@@ -16,6 +16,13 @@ number and each with its own roofline:
   train_step / train_step_bf16   fwd+bwd of one 4096-ray patch batch (perturb=1, noise_std=1)
   train_dp                   the data-parallel training leg: per-rank 4096-ray patch -> backward -> ONE all-reduce of the
                              flat gradient buffer (RCCL when N>1) -> fused Adam; replicas asserted identical
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warm-up steps, N timed steps and
+the JSON line (its `roofline.traffic` comes from the committed profile when that was measured on these kernel sources, else null).
+Everything else above -- the live rocprofv3 PMC passes, `cpu_baseline`, `torch_eager_gpu_baseline`, `records`, `train_*` -- runs
+only with `--full` (and there as before: `--no-extra`, `--no-cpu-baseline`, `--no-pmc` leave parts of it out).
+`--dump-outputs DIR` writes what the last timed step returned (the render_rays dict of rank 0) as DIR/<key>.npy; the inputs are
+seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -63,9 +70,9 @@ def build_models(O, dev, dtype, train=False):
     return models, params
 
 
-def time_render(models, emb, rays, NS, NI, steps, warmup, barrier=None):
+def time_render(models, emb, rays, NS, NI, steps, warmup, barrier=None, last=None):
     """`steps` eval renders of `rays`; returns (seconds for all steps, fine-launch ms, coarse-launch ms) with the MLP launches
-    timed by HIP events on the launch stream (rendering.PROFILE)."""
+    timed by HIP events on the launch stream (rendering.PROFILE).  `last`: a dict that receives the last timed step's outputs."""
     from sinnerf_amd import rendering
     n_rays = rays.shape[0]
 
@@ -84,9 +91,42 @@ def time_render(models, emb, rays, NS, NI, steps, warmup, barrier=None):
     dt = time.perf_counter() - t0
     prof, rendering.PROFILE = rendering.PROFILE, None
     assert all(torch.isfinite(v).all() for v in out.values())
+    if last is not None:
+        last.update(out)
     fine = [e0.elapsed_time(e1) for (n, so, e0, e1) in prof if n == n_rays * (NS + NI)]
     coarse = [e0.elapsed_time(e1) for (n, so, e0, e1) in prof if n == n_rays * NS]
     return dt, float(np.mean(fine)), float(np.mean(coarse))
+
+
+DUMP_LIMIT_BYTES = 48 * 2 ** 20          # array bytes: with the .npy headers and manifest.json the files stay under 64 MB
+DUMP_WHOLE_BYTES = 4 * 2 ** 20
+
+
+def dump_outputs(out, path, seed=0):
+    """--dump-outputs: every entry of `out` (the render_rays dict of the last timed step) as `path`/<key>.npy, float32 (float64 stays
+    float64).  When the whole dict exceeds DUMP_LIMIT_BYTES, entries up to DUMP_WHOLE_BYTES are still written whole and the larger
+    ones keep one fixed, seeded subset of their rows (the same rows for every such entry, every run); `manifest.json` says which."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for k, v in out.items():
+        a = v.detach().cpu()
+        arrs[k] = (a.double() if a.dtype in (torch.float64, torch.int64, torch.int32) else a.float()).numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    big = [k for k, a in arrs.items() if total > DUMP_LIMIT_BYTES and a.nbytes > DUMP_WHOLE_BYTES and a.ndim > 0]
+    man = {"entries": {}, "sample_seed": seed}
+    if big:
+        room = DUMP_LIMIT_BYTES - sum(a.nbytes for k, a in arrs.items() if k not in big)
+        n = min(arrs[k].shape[0] for k in big)
+        per_row = sum(arrs[k].nbytes // arrs[k].shape[0] for k in big)
+        rows = np.sort(np.random.default_rng(seed).choice(n, min(n, max(1, room // per_row)), replace=False))
+        for k in big:
+            man["entries"][k] = {"shape": list(arrs[k].shape), "rows": "seeded sample of %d of %d" % (rows.size, arrs[k].shape[0])}
+            arrs[k] = np.ascontiguousarray(arrs[k][rows])
+    for k, a in arrs.items():
+        man["entries"].setdefault(k, {"shape": list(a.shape), "rows": "all"})["dtype"] = str(a.dtype)
+        np.save(os.path.join(path, k + ".npy"), a)
+    with open(os.path.join(path, "manifest.json"), "w") as f:
+        json.dump(man, f, indent=1)
 
 
 def roofline_record(dtype, n_rays, NS, NI, ms_fine, ms_coarse, ms_step, traffic=None, traffic_note=None):
@@ -188,9 +228,9 @@ def live_pmc_traffic(args, n_points, timeout=120):
 
 
 def pmc_traffic(n_points, dtype, args=None):
-    """`roofline.traffic`: HBM bytes of the fine-pass launch.  Measured live (live_pmc_traffic) unless --no-pmc; otherwise / on failure
-    the committed profile is used ONLY IF it was measured on these kernel sources (kernel_sources_sha) -- a stale profile yields null."""
-    why = "--no-pmc"
+    """`roofline.traffic`: HBM bytes of the fine-pass launch.  Measured live (live_pmc_traffic) with --full unless --no-pmc; otherwise / on
+    failure the committed profile is used ONLY IF it was measured on these kernel sources (kernel_sources_sha) -- a stale profile yields null."""
+    why = "--no-pmc" if args is not None and args.no_pmc else "no live PMC pass without --full"
     if args is not None and not args.no_pmc:
         got, why = live_pmc_traffic(args, n_points)
         if got is not None:
@@ -837,7 +877,10 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="developer option: 'gloo' lets N ranks share one GPU for testing")
     ap.add_argument("--selftest-launcher", action="store_true", help="rendezvous + all-reduce only, no GPU work (CPU test)")
     ap.add_argument("--full-json", default=None, help="also write the un-shortened result (every record, every note) to this file; "
-                                                       "default gpurun_out/bench_full_<dtype>_n<N>.json when gpurun_out/ can be created")
+                                                       "with --full it defaults to bench_full_<dtype>_n<N>.json in the run-output folder")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: live PMC passes, CPU and eager-GPU "
+                                                       "baselines, other precisions and configs, training legs (off: the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -901,7 +944,11 @@ def main():
             dist.barrier(device_ids=[local]) if args.dist_backend == "nccl" else dist.barrier()
         torch.cuda.synchronize()
 
-    dt, ms_fine, ms_coarse = time_render(models, emb, rays, NS, NI, args.steps, args.warmup, barrier)
+    last = {}
+    dt, ms_fine, ms_coarse = time_render(models, emb, rays, NS, NI, args.steps, args.warmup, barrier, last=last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    del last
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -911,7 +958,7 @@ def main():
     if rank == 0:
         total_rays = n_rays * world * args.steps
         value = total_rays / dt
-        traffic, traffic_note = pmc_traffic(n_rays * (NS + NI), args.dtype, args if world == 1 else None)
+        traffic, traffic_note = pmc_traffic(n_rays * (NS + NI), args.dtype, args if world == 1 and args.full else None)
         res = {
             "metric": "rendered rays/sec (64+%d samples), lego %dx%d" % (NI, W, H),
             "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -927,7 +974,7 @@ def main():
         }
 
     # ---- the data-parallel training leg (every rank takes part; it is the only place a collective runs) ----------------
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         try:
             # (a 3.5 ms step: 5 warm-up + >= 20 timed steps -- a 2 + 5 run measures 7 % of ramp-up, tools/dp_leg_time.py; the
             # all-reduce time is the mean over those >= 20 steps)
@@ -950,7 +997,7 @@ def main():
             if leg32 is not None:
                 res["train_dp_fp32"] = leg32
 
-    if world > 1 and not args.no_extra:
+    if world > 1 and args.full and not args.no_extra:
         # ---- the named multi-GPU configs (BASELINE configs[3], configs[4]) as the sharded workloads they are: every rank takes part
         recs = {}
         if rank == 0:                                # the headline is measured: keep it legible even if a record below takes the job down
@@ -970,7 +1017,7 @@ def main():
         if rank == 0:
             res["records"] = recs
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         # ---- secondary records: other precisions / configs, each with its own roofline (never the headline `value`) ----
         records = {}
         try:
@@ -1039,7 +1086,7 @@ def main():
             records["train_cfg3_full_bf16"] = {"error": repr(e)}
         torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # ---- CPU baseline: the reference's op sequence (models/rendering.py:126-335 + models/nerf.py) as stock torch ops on
         # the reference's own runtime -- torch CPU, all host cores -- on a bounded sample of the same frame (oracle/torch_ref.py;
         # /root/reference itself cannot travel to the GPU box).  The numpy restatement is kept as a secondary figure.
@@ -1170,13 +1217,14 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:                      # noqa: BLE001
             res["torch_eager_gpu_baseline"] = {"error": repr(e)}
-    if rank == 0:
+    if rank == 0 and (args.full or args.full_json):
         full = args.full_json or os.path.join(REPO, "gpurun_out", "bench_full_%s_n%d.json" % (args.dtype, world))
         try:
             os.makedirs(os.path.dirname(full), exist_ok=True)
             json.dump(res, open(full, "w"), indent=1)
         except OSError:
             pass
+    if rank == 0:
         print(json.dumps(compact_line(res)))
     if world > 1:
         dist.destroy_process_group()

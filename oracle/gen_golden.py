@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate golden vectors from the UNMODIFIED reference (run in the build container only).
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [--grads | --rays | --loss | --pfm | --classic-heads]
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [--grads | --rays | --loss | --pfm | --classic-heads | --trained | --port-check]
 
 Imports ``models.rendering`` / ``models.nerf`` straight from ``/root/reference`` (read-only mount,
 never present on the GPU box), executes them on CPU/fp32 with seeded synthetic inputs and stores
@@ -165,7 +165,7 @@ def main():
     print("done ->", OUT)
 
 
-if __name__ == "__main__" and not any(f in sys.argv for f in ("--grads", "--rays", "--loss", "--pfm", "--classic-heads", "--trained")):
+if __name__ == "__main__" and not any(f in sys.argv for f in ("--grads", "--rays", "--loss", "--pfm", "--classic-heads", "--trained", "--port-check")):
     main()
 
 
@@ -415,3 +415,25 @@ def main_trained():
 
 if __name__ == "__main__" and "--trained" in sys.argv:
     main_trained()
+
+
+def main_port_check():
+    """tests/test_ref_stage_cpu.py's fixture: the reference eval render (teacher seeds 0 / 1, 64+64, white_back) of 192 lego rays,
+    and the sha256 of every file oracle/stage_ref.py stages -- what the port and a staged copy are held to without the reference."""
+    import hashlib
+    import json
+    from oracle import stage_ref
+    models = [ref_model(s, True)[0] for s in (0, 1)]
+    rays = torch.from_numpy(O.lego_rays(400, 400, seed=0)[::700][:192].copy())
+    with torch.no_grad():
+        r = ref_rendering.render_rays(models, [Embedding(3, 10), Embedding(3, 4)], rays, 64, False, 0, 0, 64, 32768, True)
+    np.savez_compressed(os.path.join(OUT, "render_lego_eval_192.npz"),
+                        **{k: r[k].numpy().astype(np.float32) for k in ("rgb_coarse", "rgb_fine", "depth_coarse", "depth_fine")})
+    files = {f: hashlib.sha256(open(os.path.join(REF, f), "rb").read()).hexdigest()
+             for f in stage_ref.FILES + stage_ref.CALLER_FILES if os.path.isfile(os.path.join(REF, f))}
+    with open(os.path.join(OUT, "reference_files_sha256.json"), "w") as f:
+        json.dump({"note": "sha256 of the reference files that oracle/stage_ref.py stages into oracle/_ref", "files": files}, f, indent=1)
+
+
+if __name__ == "__main__" and "--port-check" in sys.argv:
+    main_port_check()

@@ -120,3 +120,29 @@ def test_no_roofline_fraction_can_exceed_one():
         pass
     else:
         raise AssertionError("compact_line accepted a fraction above 1")
+
+
+def test_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """--dump-outputs: one .npy per returned entry (float32, float64 kept); small entries whole, wide ones cut to the SAME seeded rows on every run,
+    all of it under 64 MB."""
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    out = {"rgb_fine": torch.rand(160000, 3, generator=g), "depth_fine": torch.rand(160000, generator=g, dtype=torch.float64),
+           "opacity_coarse": torch.rand(160000, 64, generator=g), "opacity_fine": torch.rand(160000, 128, generator=g)}
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["depth_fine.npy", "manifest.json", "opacity_coarse.npy", "opacity_fine.npy", "rgb_fine.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 * 10 ** 6
+    for f in files[:1] + files[2:]:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    assert np.array_equal(np.load(tmp_path / "a" / "rgb_fine.npy"), out["rgb_fine"].numpy())
+    assert np.load(tmp_path / "a" / "depth_fine.npy").dtype == np.float64
+    wide = np.load(tmp_path / "a" / "opacity_fine.npy")
+    assert 0 < wide.shape[0] < 160000 and wide.shape[1] == 128
+    rows = [int(np.flatnonzero((out["opacity_fine"].numpy() == r).all(1))[0]) for r in wide[:3]]
+    assert np.array_equal(np.load(tmp_path / "a" / "opacity_coarse.npy")[:3], out["opacity_coarse"].numpy()[rows])

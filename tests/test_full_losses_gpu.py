@@ -27,8 +27,7 @@ PSX, PSY = 63, 84                                                               
 
 def _discriminator(seed=0):
     if not stage_ref.discriminator_available():
-        if stage_ref.stage() is None or not stage_ref.discriminator_available():
-            pytest.skip("oracle/_ref does not hold models/discriminator.py (build() stages it where /root/reference exists)")
+        pytest.skip("oracle/_ref does not hold models/discriminator.py (build() stages it where a checkout of the reference is present)")
     mod = stage_ref.load_discriminator()
     torch.manual_seed(seed)
     # sinnerf.py:144-145 with --patch_size unset (-1) as in the LLFF commands: the generic branch, logits (1, 1, 12, 18) for a 63 x 84 patch

@@ -206,7 +206,7 @@ def test_bench_self_launch_two_gloo_ranks_one_gpu():
     """`python bench.py --gpus 2 --dist-backend gloo` with NO external launcher on a 1-GPU box: both ranks render, the
     data-parallel training leg runs its all-reduce across the two ranks and the replicas stay identical."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "1",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "1",
                           "--warmup", "1", "--hw", "120", "120", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
