@@ -20,7 +20,9 @@ extern "C" {
 #define SN_ABI_VERSION 5   /* 2: sn_sample_pdf_bins gained eps, dtype carries SN_DTYPE_CLASSIC_HEADS, sn_mlp_forward flag bits
                             * 3: dtype carries SN_DTYPE_COMPILER_SCHEDULED and SN_DTYPE_EMB_BF16
                             * 4: SN_DTYPE_BF16X3 (inference and training entries, packers), sn_pack_table_entries_dtype
-                            * 5: SN_DTYPE_F16 (inference entries, packer), SN_FLAG_F32_LDS_RING */
+                            * 5: SN_DTYPE_F16 (inference entries, packer), SN_FLAG_F32_LDS_RING
+                            *    (additive within 5: the pose-gradient entries sn_ray_grads, sn_ray_grads_workspace_bytes,
+                            *    sn_composite_backward_rays, sn_generate_rays_backward and its workspace query) */
 
 #define SN_DTYPE_F32 0  /* v_mfma_f32_32x32x2_f32, exact fp32                                          */
 #define SN_DTYPE_BF16 1 /* v_mfma_f32_32x32x16_bf16, bf16 operands / fp32 accumulate                    */
@@ -208,6 +210,39 @@ int sn_composite_backward(const float* raw, const float* z_vals, const float* ra
                           long n_rays, int n_samples, int white_back, const float* g_rgb, const float* g_depth,
                           const float* g_weights, float* g_raw, void* stream);
 
+/* ==== gradients with respect to the RAYS (additive within ABI 5) ==============================================
+ * The reference's render_rays is an ordinary differentiable function of its rays (pose refinement, iNeRF-style registration);
+ * the three entries below are what autograd derives for one render pass with z_vals held constant (the coarse depths depend on
+ * near / far only, rendering.py:264-282; the fine ones are detached at :312).  near / far themselves (columns 6, 7) are treated as
+ * constants: their gradient columns are written as zeros.
+ *
+ * ---- backward of models/nerf.py:36-41 (Embedding) + :122-148 (the three layers that read the embedded input) + the point
+ * construction xyz = o + d z, dir = d of rendering.py:187-190, :284-285, summed over the samples of each ray:
+ *   g_emb_xyz = G0 . W1 + G4 . W5[:, 0:63]   (nerf.py:133: the skip input is cat([input_xyz, h]))
+ *   g_emb_dir = G9[:, 0:128] . Wdir[:, 256:283]   (nerf.py:142: cat([xyz_encoding_final, input_dir]))
+ *   g_x = ge[0:3] + sum_k 2^k (cos(2^k x) ge[3+6k : 6+6k] - sin(2^k x) ge[6+6k : 9+6k])   (k < 10 at xyz, k < 4 at d; sin / cos recomputed)
+ *   g_rays[r, 0:3] = sum_s g_xyz[r, s]       g_rays[r, 3:6] = sum_s z[r, s] g_xyz[r, s] + sum_s g_dirvec[r, s]       g_rays[r, 6:8] = 0
+ * w1 = xyz_encoding_1.0.weight (256 x 63), w5 = xyz_encoding_5.0.weight (256 x 319), wdir = dir_encoding.0.weight (128 x 283): the raw
+ * fp32 parameter tensors, row-major (no packed blob).  g_acts / slot_rows: as written by sn_mlp_backward_chain; only slots 0, 4 and 9
+ * and only rows < n_rays * n_samples are read.  dtype names the LAYOUT that chain left: SN_DTYPE_F32 / SN_DTYPE_BF16 (fp32 rows),
+ * SN_DTYPE_BF16_STATE (bf16 rows), SN_DTYPE_BF16X3 (slots 0 and 4 as (hi, lo) pairs -- the value used is hi + lo -- slot 9 fp32); anything
+ * else, flag bits included, is SN_E_UNSUPPORTED.  The arithmetic is fp32 (v_mfma_f32_32x32x2_f32) whatever the layout.
+ * g_rays (n_rays, 8) is WRITTEN (not accumulated); the sums over samples run in a fixed order without atomics, so two calls give the
+ * same bits.  n_samples in 1..1024.  workspace: sn_ray_grads_workspace_bytes(n_rays, n_samples) bytes of DEVICE scratch.
+ * The compositor's own contribution to g_rays[:, 3:6] (through ||d||) comes from sn_composite_backward_rays; add the two.     */
+long sn_ray_grads_workspace_bytes(long n_rays, int n_samples);
+int sn_ray_grads(const float* w1, const float* w5, const float* wdir, int dtype, const void* g_acts, long slot_rows,
+                 const float* rays, const float* z_vals, long n_rays, int n_samples, void* workspace, float* g_rays,
+                 void* stream);
+
+/* ---- sn_composite_backward + the gradient through deltas = dz * ||d|| (models/rendering.py:215-222, :228):
+ *   dL/d||d|| = sum_i dL/dalpha_i exp(-delta_i s_i) max(sigma_i + noise_i, 0) dz_i     (dz_i = z_{i+1} - z_i, 1e10 for the last sample)
+ *   g_rays[r, 3:6] = dL/d||d|| * d / ||d||   (0 for a ray with ||d|| = 0),   every other column 0.
+ * g_raw receives the same bits sn_composite_backward writes (one kernel body); g_rays (n_rays, 8) is written.                   */
+int sn_composite_backward_rays(const float* raw, const float* z_vals, const float* rays, const float* noise, float noise_std,
+                               long n_rays, int n_samples, int white_back, const float* g_rgb, const float* g_depth,
+                               const float* g_weights, float* g_raw, float* g_rays, void* stream);
+
 /* ---- models/nerf.py:105-148  NeRF.forward(x, sigma_only) on an already embedded matrix --------------------
  * x (n_rows, ld) with columns [0,63) = embedded xyz and [63,90) = embedded dir (ignored when sigma_only).   */
 int sn_mlp_forward_embedded(const void* blob, int dtype, const float* x, long n_rows, int ld, int sigma_only,
@@ -242,6 +277,16 @@ int sn_sample_pdf_bins(const float* bins, const float* weights, const float* u, 
  * written row-major over (iy, ix) into rays (patch_w*patch_h, 8).  Full frame = (0, 0, 1, 1, W, H).             */
 int sn_generate_rays(const float* c2w, int H, int W, float focal, float near, float far, int x0, int y0, int stride_x,
                      int stride_y, int patch_w, int patch_h, float* rays, void* stream);
+
+/* ---- backward of sn_generate_rays with respect to c2w (datasets/ray_utils.py:109, :112: rays_d = directions @ c2w[:, :3].T,
+ * rays_o = c2w[:, 3]):  g_c2w[a][b] = sum_rays g_rays[r, 3 + a] * dir_cam_r[b]  (b < 3),  g_c2w[a][3] = sum_rays g_rays[r, a], with
+ * dir_cam = ((x - W/2) / focal, -(y - H/2) / focal, -1) of the pixel of that row (ray_utils.py:89-91).  g_rays (patch_w * patch_h, 8):
+ * the upstream gradient of the rays (columns 6, 7 ignored); window arguments as for sn_generate_rays.  g_c2w: 12 floats (3x4
+ * row-major, DEVICE), written.  workspace: sn_generate_rays_backward_workspace_bytes bytes of DEVICE scratch (per-block fp64
+ * partial sums, added in a fixed order: deterministic).                                                                */
+long sn_generate_rays_backward_workspace_bytes(void);
+int sn_generate_rays_backward(const float* g_rays, int H, int W, float focal, int x0, int y0, int stride_x, int stride_y,
+                              int patch_w, int patch_h, void* workspace, float* g_c2w, void* stream);
 
 /* ---- utils/__init__.py:19-21 (torch.optim.Adam, eps=1e-8) over one flat fp32 buffer (the all-reduce buffer).
  * step = 1-based iteration count (bias correction).                                                             */

@@ -6,9 +6,12 @@ two ``torch.autograd.Function``s stand in for the two differentiable stages, so 
 an ordinary autograd graph whose leaves are the ``NeRF`` parameters (DDP hooks / optimisers work unchanged):
 
   _MLPFn        sn_mlp_forward_train  ->  sn_mlp_backward_chain  ->  dW_l = g_l^T X_l  (big-K GEMMs), db_l = sum g_l
-  _CompositeFn  sn_composite_forward  ->  sn_composite_backward
+                                                                 ->  sn_ray_grads (only when ``rays`` requires grad)
+  _CompositeFn  sn_composite_forward  ->  sn_composite_backward  (sn_composite_backward_rays when ``rays`` requires grad)
 
-``sample_pdf`` is detached as in the reference (``rendering.py:312``); rays / depths are data (no gradient).
+``sample_pdf`` is detached as in the reference (``rendering.py:312``); the sample depths are data (no gradient).  The rays are
+differentiable in their origins and directions (columns 0..5) when they require grad: pose refinement / registration optimise
+``c2w`` through ``ray_utils.get_rays`` -> ``render_rays``.  near / far (columns 6, 7) are constants: their gradient is zero.
 """
 import torch
 
@@ -96,9 +99,32 @@ def _weight_grads(model, acts, emb, G, needs):
     return [None] * len(outs) if sink is not None else outs
 
 
+def _ray_grads(model, G, rows, rays, z_vals):
+    """dL/d(rays) of one MLP pass from the pre-activation gradients the chain left in ``G`` (``sn_ray_grads``): (N, 8), columns
+    6, 7 zero."""
+    n, s = z_vals.shape
+    raws = model.raw_tensors()
+    w1, w5, wdir = (raws[i].detach().contiguous().float() for i in (0, 8, 18))     # xyz_encoding_1 / _5 / dir_encoding weights
+    code = _state_code(model, G) & ~_lib.SN_DTYPE_EMB_BF16
+    nbytes = _lib.lib.sn_ray_grads_workspace_bytes(n, s)
+    if nbytes < 0:
+        _lib.check(int(nbytes), "sn_ray_grads_workspace_bytes")
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=G.device)
+    g_rays = torch.empty((n, 8), dtype=torch.float32, device=G.device)
+    _lib.check(_lib.lib.sn_ray_grads(_lib.ptr(w1), _lib.ptr(w5), _lib.ptr(wdir), code, _lib.ptr(G), rows, _lib.ptr(rays), _lib.ptr(z_vals),
+                                     n, s, _lib.ptr(ws), _lib.ptr(g_rays), _lib.stream_ptr()), "sn_ray_grads")
+    return g_rays
+
+
 class _MLPFn(torch.autograd.Function):
     """rays mode: (rays (N,8), z_vals (N,S)) -> raw (N,S,4).  Embedded mode (``z_vals is None``): ``rays`` is the
-    pre-embedded (B, 90) matrix of ``NeRF.forward`` (nerf.py:105-148) -> (B, 4)."""
+    pre-embedded (B, 90) matrix of ``NeRF.forward`` (nerf.py:105-148) -> (B, 4).
+
+    rays mode is differentiable in ``rays`` as well (``sn_ray_grads``: the contraction of the stored pre-activation gradients of
+    xyz_encoding_1 / _5 / dir_encoding with their weights, the Embedding derivative, the sum over a ray's samples): columns 0..2 =
+    origin, 3..5 = direction through xyz = o + d z and through Embedding(d).  Limitation: near / far (columns 6, 7) are treated as
+    constants -- their gradient columns are zero; the reference would differentiate the coarse depths through them, no reference
+    call site does.  ``z_vals`` is data.  Embedded mode has no input gradient."""
 
     @staticmethod
     def forward(ctx, model, rays, z_vals, *params):
@@ -138,12 +164,16 @@ class _MLPFn(torch.autograd.Function):
                        "sn_mlp_forward_train")
         ctx.model = model
         ctx.n_points = P
-        ctx.save_for_backward(acts, emb, out)
+        ctx.rays_grad = (not embedded) and bool(ctx.needs_input_grad[1])
+        if ctx.rays_grad:
+            ctx.save_for_backward(acts, emb, out, rays, z_vals)
+        else:
+            ctx.save_for_backward(acts, emb, out)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        acts, emb, out = ctx.saved_tensors
+        acts, emb, out = ctx.saved_tensors[:3]
         model = ctx.model
         P, rows = ctx.n_points, acts.shape[1]
         dev = acts.device
@@ -161,8 +191,10 @@ class _MLPFn(torch.autograd.Function):
                                                       _lib.ptr(acts), _lib.ptr(out), _lib.ptr(g_out), P, rows, _lib.ptr(G),
                                                       _lib.ptr(g_o), _lib.stream_ptr()), "sn_mlp_backward_chain")
             needs = ctx.needs_input_grad[3:]
-            grads = _weight_grads(model, acts, emb, G, needs)
-        return (None, None, None, *grads)
+            # (a frozen network under pose optimisation: no weight-gradient launches at all)
+            grads = _weight_grads(model, acts, emb, G, needs) if any(needs) else [None] * len(needs)
+            g_rays = _ray_grads(model, G, rows, *ctx.saved_tensors[3:]) if ctx.rays_grad else None
+        return (None, g_rays, None, *grads)
 
 
 class _CompositeFn(torch.autograd.Function):
@@ -190,17 +222,26 @@ class _CompositeFn(torch.autograd.Function):
         g_raw = torch.empty((n, s, 4), dtype=torch.float32, device=raw.device)
         c = lambda t: None if t is None else t.contiguous().float()
         g_rgb, g_depth, g_w = c(g_rgb), c(g_depth), c(g_w)
+        g_rays = None
         with torch.cuda.device(raw.device):
-            _lib.check(_lib.lib.sn_composite_backward(_lib.ptr(raw), _lib.ptr(z_vals), _lib.ptr(rays),
-                                                      _lib.ptr(noise) if ctx.has_noise else None, ctx.noise_std, n, s,
-                                                      ctx.white_back, _lib.ptr(g_rgb), _lib.ptr(g_depth), _lib.ptr(g_w),
-                                                      _lib.ptr(g_raw), _lib.stream_ptr()), "sn_composite_backward")
-        return g_raw, None, None, None, None, None
+            if ctx.needs_input_grad[2]:              # the rays through deltas = dz * ||d|| (rendering.py:222): columns 3..5
+                g_rays = torch.empty((n, 8), dtype=torch.float32, device=raw.device)
+                _lib.check(_lib.lib.sn_composite_backward_rays(_lib.ptr(raw), _lib.ptr(z_vals), _lib.ptr(rays),
+                                                               _lib.ptr(noise) if ctx.has_noise else None, ctx.noise_std, n, s,
+                                                               ctx.white_back, _lib.ptr(g_rgb), _lib.ptr(g_depth), _lib.ptr(g_w),
+                                                               _lib.ptr(g_raw), _lib.ptr(g_rays), _lib.stream_ptr()),
+                           "sn_composite_backward_rays")
+            else:
+                _lib.check(_lib.lib.sn_composite_backward(_lib.ptr(raw), _lib.ptr(z_vals), _lib.ptr(rays),
+                                                          _lib.ptr(noise) if ctx.has_noise else None, ctx.noise_std, n, s,
+                                                          ctx.white_back, _lib.ptr(g_rgb), _lib.ptr(g_depth), _lib.ptr(g_w),
+                                                          _lib.ptr(g_raw), _lib.stream_ptr()), "sn_composite_backward")
+        return g_raw, None, g_rays, None, None, None
 
 
 def render_rays_autograd(models, rays, N_samples, use_disp, perturb, noise_std, N_importance, white_back, test_time,
                          detach_coarse):
-    """Differentiable ``render_rays`` (called by ``rendering.render_rays`` when a model parameter requires grad).
+    """Differentiable ``render_rays`` (called by ``rendering.render_rays`` when a model parameter or ``rays`` requires grad).
     Same stage order and RNG consumption as ``rendering._forward_core``."""
     from . import rendering as R
     dev = rays.device
@@ -215,7 +256,8 @@ def render_rays_autograd(models, rays, N_samples, use_disp, perturb, noise_std, 
     _lib.check(_lib.lib.sn_sample_coarse(_lib.ptr(rays), n, N_samples, int(bool(use_disp)), float(perturb),
                                          _lib.ptr(perturb_rand), _lib.ptr(z_vals), stream), "sn_sample_coarse")
     result = {}
-    coarse_grad = (not detach_coarse) and (not test_time) and any(p.requires_grad for p in models[0].parameters())
+    rays_grad = rays.requires_grad
+    coarse_grad = (not detach_coarse) and (not test_time) and (rays_grad or any(p.requires_grad for p in models[0].parameters()))
     if test_time:
         # weights-only coarse pass (rendering.py:287-291); its only consumer is the detached sample_pdf
         with torch.no_grad():
@@ -243,7 +285,7 @@ def render_rays_autograd(models, rays, N_samples, use_disp, perturb, noise_std, 
         z_all = torch.empty((n, N_samples + N_importance), dtype=torch.float32, device=dev)
         _lib.check(_lib.lib.sn_sample_pdf(_lib.ptr(z_vals), _lib.ptr(w_c.detach()), _lib.ptr(u), n, N_samples,
                                           N_importance, None, _lib.ptr(z_all), stream), "sn_sample_pdf")
-        if any(p.requires_grad for p in models[1].parameters()):
+        if rays_grad or any(p.requires_grad for p in models[1].parameters()):
             raw_f = _MLPFn.apply(models[1], rays, z_all, *models[1].raw_tensors())
         else:
             with torch.no_grad():

@@ -95,6 +95,16 @@ int sn_mlp_backward_chain_bf16_t_classic_launch(const void* bblob, const float* 
 int sn_composite_backward_launch(const float* raw, const float* z_vals, const float* rays, const float* noise,
                                  float noise_std, long n_rays, int n_samples, int white_back, const float* g_rgb,
                                  const float* g_depth, const float* g_w, float* g_raw, hipStream_t stream);
+int sn_composite_backward_rays_launch(const float* raw, const float* z_vals, const float* rays, const float* noise,
+                                      float noise_std, long n_rays, int n_samples, int white_back, const float* g_rgb,
+                                      const float* g_depth, const float* g_w, float* g_raw, float* g_rays, hipStream_t stream);
+long sn_ray_grads_workspace_bytes_impl(long n_rays, int n_samples);
+int sn_ray_grads_launch(const float* w1, const float* w5, const float* wdir, int layout, const void* g_acts, long slot_rows,
+                        const float* rays, const float* z_vals, long n_rays, int n_samples, void* workspace, float* g_rays,
+                        hipStream_t stream);
+long sn_generate_rays_backward_workspace_bytes_impl();
+int sn_generate_rays_backward_launch(const float* g_rays, int H, int W, float focal, int x0, int y0, int sx, int sy, int pw,
+                                     int ph, void* workspace, float* g_c2w, hipStream_t stream);
 int sn_sample_coarse_launch(const float* rays, long n_rays, int n_samples, int use_disp, float perturb,
                             const float* perturb_rand, float* z_out, hipStream_t stream);
 int sn_composite_forward_launch(const float* raw, int has_rgb, const float* z_vals, const float* rays,
@@ -393,6 +403,47 @@ int sn_composite_backward(const float* raw, const float* z_vals, const float* ra
   if (!raw || !z_vals || !rays || !g_raw || n_rays < 0 || n_samples < 1) return SN_E_BADARG;
   return sn_composite_backward_launch(raw, z_vals, rays, noise, noise_std, n_rays, n_samples, white_back, g_rgb, g_depth,
                                       g_weights, g_raw, (hipStream_t)stream);
+}
+
+int sn_composite_backward_rays(const float* raw, const float* z_vals, const float* rays, const float* noise, float noise_std,
+                               long n_rays, int n_samples, int white_back, const float* g_rgb, const float* g_depth,
+                               const float* g_weights, float* g_raw, float* g_rays, void* stream) {
+  if (!raw || !z_vals || !rays || !g_raw || !g_rays || n_rays < 0 || n_samples < 1) return SN_E_BADARG;
+  return sn_composite_backward_rays_launch(raw, z_vals, rays, noise, noise_std, n_rays, n_samples, white_back, g_rgb, g_depth,
+                                           g_weights, g_raw, g_rays, (hipStream_t)stream);
+}
+
+long sn_ray_grads_workspace_bytes(long n_rays, int n_samples) {
+  if (n_rays < 0 || n_samples < 1 || n_samples > 1024) return SN_E_BADSHAPE;
+  return sn_ray_grads_workspace_bytes_impl(n_rays, n_samples);
+}
+
+int sn_ray_grads(const float* w1, const float* w5, const float* wdir, int dtype, const void* g_acts, long slot_rows,
+                 const float* rays, const float* z_vals, long n_rays, int n_samples, void* workspace, float* g_rays,
+                 void* stream) {
+  if (!w1 || !w5 || !wdir || !g_acts || !rays || !z_vals || !workspace || !g_rays || n_rays < 0) return SN_E_BADARG;
+  if (n_samples < 1 || n_samples > 1024) return SN_E_BADSHAPE;
+  if (slot_rows < n_rays * (long)n_samples) return SN_E_BADSHAPE;
+  // the layout sn_mlp_backward_chain(dtype) left g_acts in; no flag bits: the heads and the kernel generation do not change it
+  int layout;
+  if (dtype == SN_DTYPE_F32 || dtype == SN_DTYPE_BF16) layout = 0;
+  else if (dtype == SN_DTYPE_BF16_STATE) layout = 1;
+  else if (dtype == SN_DTYPE_BF16X3) layout = 2;
+  else return SN_E_UNSUPPORTED;
+  return sn_ray_grads_launch(w1, w5, wdir, layout, g_acts, slot_rows, rays, z_vals, n_rays, n_samples, workspace, g_rays,
+                             (hipStream_t)stream);
+}
+
+long sn_generate_rays_backward_workspace_bytes(void) { return sn_generate_rays_backward_workspace_bytes_impl(); }
+
+int sn_generate_rays_backward(const float* g_rays, int H, int W, float focal, int x0, int y0, int stride_x, int stride_y,
+                              int patch_w, int patch_h, void* workspace, float* g_c2w, void* stream) {
+  if (!g_rays || !workspace || !g_c2w || H < 1 || W < 1 || stride_x < 1 || stride_y < 1 || patch_w < 0 || patch_h < 0)
+    return SN_E_BADARG;
+  if (x0 < 0 || y0 < 0 || (patch_w > 0 && x0 + (patch_w - 1) * stride_x >= W) || (patch_h > 0 && y0 + (patch_h - 1) * stride_y >= H))
+    return SN_E_BADSHAPE;
+  return sn_generate_rays_backward_launch(g_rays, H, W, focal, x0, y0, stride_x, stride_y, patch_w, patch_h, workspace, g_c2w,
+                                          (hipStream_t)stream);
 }
 
 int sn_mlp_forward_embedded(const void* blob, int dtype, const float* x, long n_rows, int ld, int sigma_only,

@@ -5,6 +5,7 @@
 //                          rays are produced ON the GPU from (c2w, focal) -- no (H*W, 8) host array, no H2D copy.
 //   adam_kernel            utils/__init__.py:19-21 (torch.optim.Adam, eps=1e-8) over ONE flat parameter/gradient buffer
 //                          (the buffer the single RCCL all-reduce runs on): one elementwise launch per step.
+//   rays_bwd_*_kernel      the backward of generate_rays_kernel w.r.t. c2w (pose gradients): 12 deterministic sums over the rays.
 //   loss_partials_kernel / loss_finish_kernel
 //                          the losses computed on the rendered rays right after the path: MSE coarse + fine
 //                          (losses.py:12-22, nn.MSELoss mean), SmoothL1 depth coarse + fine (models/sinnerf.py:32-42 SL1Loss,
@@ -159,6 +160,49 @@ loss_finish_kernel(const float* __restrict__ rgb_c, const float* __restrict__ rg
     }
 }
 
+// ---- backward of generate_rays_kernel w.r.t. c2w (autograd of ray_utils.py:109, :112: rays_d = directions @ c2w[:, :3].T,
+// rays_o = c2w[:, 3] expanded):  g_c2w[a][b] = sum_rays g_d[a] * dir_cam[b],  g_c2w[a][3] = sum_rays g_o[a].
+// Two phases like the loss reduction above: per-block fp64 partials of the 12 sums over a grid-stride share, then one block
+// adds the <= RAYS_BWD_BLOCKS partials in index order -- deterministic, no atomics.
+constexpr int RAYS_BWD_BLOCKS = 256;
+
+__global__ void __launch_bounds__(256)
+rays_bwd_partials_kernel(const float* __restrict__ g_rays, int H, int W, float focal, int x0, int y0, int sx, int sy, int pw,
+                         int ph, double* __restrict__ partials) {
+  __shared__ double sh[4];
+  const long total = (long)pw * ph;
+  const float hw = (float)W / 2.0f, hh = (float)H / 2.0f;
+  double a[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int iy = (int)(idx / pw), ix = (int)(idx - (long)iy * pw);
+    const float i = (float)(x0 + ix * sx), j = (float)(y0 + iy * sy);
+    const double d0 = (double)__fdiv_rn(__fsub_rn(i, hw), focal), d1 = (double)(-__fdiv_rn(__fsub_rn(j, hh), focal)), d2 = -1.0;
+    const float4* g = reinterpret_cast<const float4*>(g_rays + idx * 8);
+    const float4 lo = g[0], hi = g[1];
+    const double go[3] = {(double)lo.x, (double)lo.y, (double)lo.z}, gd[3] = {(double)lo.w, (double)hi.x, (double)hi.y};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      a[4 * r + 0] += gd[r] * d0; a[4 * r + 1] += gd[r] * d1; a[4 * r + 2] += gd[r] * d2; a[4 * r + 3] += go[r];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+    const double v = block_sum(a[k], sh);
+    if (threadIdx.x == 0) partials[blockIdx.x * 12 + k] = v;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+rays_bwd_finish_kernel(const double* __restrict__ partials, int n_partials, float* __restrict__ g_c2w) {
+  __shared__ double sh[4];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+    const double v = (int)threadIdx.x < n_partials ? partials[threadIdx.x * 12 + k] : 0.0;
+    const double t = block_sum(v, sh);
+    if (threadIdx.x == 0) g_c2w[k] = (float)t;
+  }
+}
+
 }  // namespace snx
 
 extern "C" int sn_generate_rays_launch(const float* c2w, int H, int W, float focal, float near, float far, int x0, int y0,
@@ -169,6 +213,21 @@ extern "C" int sn_generate_rays_launch(const float* c2w, int H, int W, float foc
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(snx::generate_rays_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, c2w, H, W, focal, near, far,
                      x0, y0, sx, sy, pw, ph, rays);
+  return (int)hipGetLastError();
+}
+
+extern "C" long sn_generate_rays_backward_workspace_bytes_impl() { return (long)snx::RAYS_BWD_BLOCKS * 12 * sizeof(double); }
+extern "C" int sn_generate_rays_backward_launch(const float* g_rays, int H, int W, float focal, int x0, int y0, int sx, int sy,
+                                                int pw, int ph, void* workspace, float* g_c2w, hipStream_t stream) {
+  using namespace snx;
+  const long total = (long)pw * ph;
+  long blocks = (total + 255) / 256;
+  if (blocks < 1) blocks = 1;                    // an empty window still writes its 12 zeros
+  if (blocks > RAYS_BWD_BLOCKS) blocks = RAYS_BWD_BLOCKS;
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(rays_bwd_partials_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, H, W, focal, x0, y0, sx, sy,
+                     pw, ph, partials);
+  hipLaunchKernelGGL(rays_bwd_finish_kernel, dim3(1), dim3(256), 0, stream, partials, (int)blocks, g_c2w);
   return (int)hipGetLastError();
 }
 

@@ -180,12 +180,15 @@ composite_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z_
 //   dL/da_i  = G_i T_i - (sum_{k>i} G_k w_k) / f_i        (cumprod backward, f_i = 1 - a_i + 1e-10 > 0)
 //   dL/ds_i  = dL/da_i * delta_i * exp(-delta_i s_i) * [sigma_i + noise_i > 0]
 // One wave per ray, same sample-to-lane mapping as the forward; suffix sum as an fp64 wave scan.
-template <int C>
-__global__ void __launch_bounds__(256)
-composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z_vals, const float* __restrict__ rays,
-                     const float* __restrict__ noise, float noise_std, long n_rays, int S, int white_back,
-                     const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_w,
-                     float* __restrict__ g_raw) {
+// RAYS (sn_composite_backward_rays): the rays are differentiable too.  d enters only through deltas = dz * ||d|| (:222), so
+//   dL/d||d|| = sum_i dL/da_i * exp(-delta_i s_i) * max(sigma_i + noise_i, 0) * dz_i      (dz_i = z_{i+1} - z_i, 1e10 for the last)
+//   dL/dd     = dL/d||d|| * d / ||d||   (torch.norm backward; 0 for ||d|| = 0)   -> g_rays[ray, 3:6], zeros elsewhere
+// g_raw is computed by the same instructions either way.
+template <int C, bool RAYS>
+SN_DEV void composite_bwd_body(const float* __restrict__ raw, const float* __restrict__ z_vals, const float* __restrict__ rays,
+                               const float* __restrict__ noise, float noise_std, long n_rays, int S, int white_back,
+                               const float* __restrict__ g_rgb, const float* __restrict__ g_depth,
+                               const float* __restrict__ g_w, float* __restrict__ g_raw, float* __restrict__ g_rays) {
   const int lane = threadIdx.x & 63;
   const long ray = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (ray >= n_rays) return;
@@ -201,6 +204,7 @@ composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z_
 #pragma unroll
   for (int c = 0; c < C + 1; ++c) zc[c] = (i0 + c < S) ? z_vals[base + i0 + c] : 0.0f;
   float alpha[C], ex[C], dl[C], Gi[C], fi[C];
+  float dzs[C], sps[C];                          // RAYS only: dz_i and max(sigma_i + noise_i, 0)
   bool pos[C];
   double fprod = 1.0;
 #pragma unroll
@@ -211,9 +215,11 @@ composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z_
     if (i < S) {
       const float4 v = reinterpret_cast<const float4*>(raw)[base + i];
       d = (i < S - 1) ? __fsub_rn(zc[c + 1], zc[c]) : 1e10f;
+      if (RAYS) dzs[c] = d;
       d = __fmul_rn(d, dnorm);
       float sp = v.w;
       if (noise != nullptr) sp = __fadd_rn(sp, __fmul_rn(noise[base + i], noise_std));
+      if (RAYS) sps[c] = fmaxf(sp, 0.0f);
       ps = sp > 0.0f;
       e = expf(__fmul_rn(-d, fmaxf(sp, 0.0f)));
       a = __fsub_rn(1.0f, e);
@@ -239,6 +245,7 @@ composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z_
   const double total = wave_sum(local);
   const double prefix_incl = wave_incl_scan_add(local, lane);
   double suffix = total - prefix_incl;            // sum over samples owned by higher lanes
+  double g_norm = 0.0;
 #pragma unroll
   for (int c = C - 1; c >= 0; --c) {
     const int i = i0 + c;
@@ -248,9 +255,39 @@ composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z_
       float4 o;
       o.x = w[c] * gr; o.y = w[c] * gg; o.z = w[c] * gb; o.w = g_sigma;
       reinterpret_cast<float4*>(g_raw)[base + i] = o;
+      if (RAYS) g_norm += (double)g_alpha * (double)ex[c] * (double)sps[c] * (double)dzs[c];
     }
     suffix += (double)Gi[c] * (double)w[c];
   }
+  if (RAYS) {
+    g_norm = wave_sum(g_norm);
+    if (lane == 0) {
+      const double k = dnorm > 0.0f ? g_norm / (double)dnorm : 0.0;
+      float4 lo, hi;
+      lo.x = lo.y = lo.z = 0.0f; lo.w = dnorm > 0.0f ? (float)(k * (double)dx) : 0.0f;
+      hi.x = dnorm > 0.0f ? (float)(k * (double)dy) : 0.0f; hi.y = dnorm > 0.0f ? (float)(k * (double)dz) : 0.0f;
+      hi.z = hi.w = 0.0f;
+      reinterpret_cast<float4*>(g_rays)[ray * 2] = lo;
+      reinterpret_cast<float4*>(g_rays)[ray * 2 + 1] = hi;
+    }
+  }
+}
+
+template <int C>
+__global__ void __launch_bounds__(256)
+composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z_vals, const float* __restrict__ rays,
+                     const float* __restrict__ noise, float noise_std, long n_rays, int S, int white_back,
+                     const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_w,
+                     float* __restrict__ g_raw) {
+  composite_bwd_body<C, false>(raw, z_vals, rays, noise, noise_std, n_rays, S, white_back, g_rgb, g_depth, g_w, g_raw, nullptr);
+}
+template <int C>
+__global__ void __launch_bounds__(256)
+composite_bwd_rays_kernel(const float* __restrict__ raw, const float* __restrict__ z_vals, const float* __restrict__ rays,
+                          const float* __restrict__ noise, float noise_std, long n_rays, int S, int white_back,
+                          const float* __restrict__ g_rgb, const float* __restrict__ g_depth, const float* __restrict__ g_w,
+                          float* __restrict__ g_raw, float* __restrict__ g_rays) {
+  composite_bwd_body<C, true>(raw, z_vals, rays, noise, noise_std, n_rays, S, white_back, g_rgb, g_depth, g_w, g_raw, g_rays);
 }
 
 // ---- importance sampler + merge --------------------------------------------------------------------
@@ -435,6 +472,29 @@ extern "C" int sn_composite_backward_launch(const float* raw, const float* z_val
   switch (C) { SN_CB(1) SN_CB(2) SN_CB(3) SN_CB(4) SN_CB(5) SN_CB(6) SN_CB(7) SN_CB(8) SN_CB(9) SN_CB(10) SN_CB(11) SN_CB(12)
                SN_CB(13) SN_CB(14) SN_CB(15) SN_CB(16) }
 #undef SN_CB
+  return (int)hipGetLastError();
+}
+
+// the same kernel body with the rays differentiable: g_raw as above + g_rays (n_rays, 8)
+extern "C" int sn_composite_backward_rays_launch(const float* raw, const float* z_vals, const float* rays, const float* noise,
+                                                 float noise_std, long n_rays, int n_samples, int white_back,
+                                                 const float* g_rgb, const float* g_depth, const float* g_w, float* g_raw,
+                                                 float* g_rays, hipStream_t stream) {
+  using namespace snr;
+  if (n_rays <= 0) return 0;
+  const int C = (n_samples + 63) / 64;
+  if (C < 1 || C > 16) return -4;
+  const long blocks = (n_rays + 3) / 4;
+  if (blocks > 0x7fffffffL) return -2;
+  dim3 grid((unsigned)blocks), block(256);
+#define SN_CBR(CC)                                                                                               \
+  case CC:                                                                                                       \
+    hipLaunchKernelGGL((composite_bwd_rays_kernel<CC>), grid, block, 0, stream, raw, z_vals, rays, noise, noise_std, n_rays, \
+                       n_samples, white_back, g_rgb, g_depth, g_w, g_raw, g_rays);                               \
+    break;
+  switch (C) { SN_CBR(1) SN_CBR(2) SN_CBR(3) SN_CBR(4) SN_CBR(5) SN_CBR(6) SN_CBR(7) SN_CBR(8) SN_CBR(9) SN_CBR(10) SN_CBR(11)
+               SN_CBR(12) SN_CBR(13) SN_CBR(14) SN_CBR(15) SN_CBR(16) }
+#undef SN_CBR
   return (int)hipGetLastError();
 }
 

@@ -187,6 +187,11 @@ def render_rays(models,
     need no point chunking and ignore it.  ``noisy_coarse`` is unused in the reference as well.  Configurations the kernels
     do not implement (other embeddings, more than 1024 samples per ray; other layer shapes are refused by the ``NeRF``
     constructor) raise ``NotImplementedError``: there is no torch-op second backend.
+
+    Under grad mode the result is differentiable in the network parameters and, when ``rays.requires_grad``, in the ray origins
+    and directions (``rays[:, 0:6]``; build the rays with ``ray_utils.get_rays`` to reach ``c2w``).  Limitation: near / far
+    (``rays[:, 6:8]``) are treated as constants -- their gradient columns are zero, where the reference would differentiate the
+    coarse depths through them (no reference call site does).  ``compute_dtype="fp16"`` is inference only.
     """
     if not isinstance(rays, torch.Tensor) or not rays.is_cuda:
         raise RuntimeError("sinnerf_amd.render_rays: rays must be a CUDA/ROCm tensor (there is no CPU fallback)")
@@ -198,6 +203,7 @@ def render_rays(models,
                             "the reference NeRF; load reference weights with load_state_dict)")
     if N_importance > 0 and len(models) < 2:
         raise IndexError("list index out of range")          # models[1], rendering.py:321
+    rays_grad = torch.is_grad_enabled() and rays.requires_grad
     rays = rays.contiguous().float()
     # one configuration exists in HIP (the one both reference call sites build); everything else is refused, loudly
     _check_embeddings(embeddings)
@@ -205,7 +211,7 @@ def render_rays(models,
         raise NotImplementedError("sinnerf_amd.render_rays: %d + %d samples per ray; the per-ray kernels (compositor, importance "
                                   "sampler, merge) hold at most %d in one wave.  Supported: %s"
                                   % (N_samples, N_importance, MAX_FUSED_SAMPLES, SUPPORTED))
-    needs_grad = torch.is_grad_enabled() and any(p.requires_grad for m in models for p in m.parameters())
+    needs_grad = rays_grad or (torch.is_grad_enabled() and any(p.requires_grad for m in models for p in m.parameters()))
     with torch.cuda.device(rays.device):
         if needs_grad and rays.shape[0] > 0:
             from .autograd import render_rays_autograd
