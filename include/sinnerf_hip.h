@@ -194,13 +194,29 @@ int sn_dw_gemm(const void* tasks, int n_tasks, void* stream);
  * nn.Linear.weight.grad / .bias.grad for models/nerf.py:66-103 (the cat of the skip / direction inputs, nerf.py:133,142,
  * becomes two column ranges of the same gradient).
  *   acts, emb: as written by sn_mlp_forward_train; g_acts: as written by sn_mlp_backward_chain (pad rows zero);
- *   slot_rows: a multiple of 16; dtype: SN_DTYPE_F32 (fp32 MFMAs), SN_DTYPE_BF16 (bf16 operands, fp32 state) or
+ *   slot_rows: any multiple of 16, >= 16; dtype: SN_DTYPE_F32 (fp32 MFMAs), SN_DTYPE_BF16 (bf16 operands, fp32 state) or
  *   SN_DTYPE_BF16_STATE (acts / g_acts stored as bf16) or SN_DTYPE_BF16X3 (the x3 state; see the PAIRING RULE at sn_mlp_backward_chain:
  *   acts / g_acts must have been written with the SAME dtype);
  *   workspace: sn_weight_grads_workspace_bytes(slot_rows, dtype) bytes of DEVICE scratch (the K-split partials);
  *   grads: HOST array of SN_N_RAW_TENSORS device pointers in the order of sn_pack_weights' `raw` (NULL = not wanted);
- *   accumulate != 0: grads[i] += result (autograd's accumulation into an existing .grad), else grads[i] = result.        */
+ *   accumulate != 0: grads[i] += result (autograd's accumulation into an existing .grad), else grads[i] = result.
+ * Pinned by tests/test_dw_plan_cpu.py and tests/test_weight_grads_edges_gpu.py:
+ *   - ANY slot_rows that is a multiple of 16 and at least 16 is supported (not only the multiples of 128 / 256 the training forward
+ *     asks for): every point is contracted exactly once, whatever the K-split makes of the size;
+ *   - the workspace need NOT be initialised: every task writes its whole partial before the finish kernel sums it (no K-range of the
+ *     plan is empty), so stale contents -- NaN bit patterns included -- never reach a gradient;
+ *   - the columns of `emb` the training forward never writes (fp32 form: 63 and 91..127; SN_DTYPE_EMB_BF16: the positions no column
+ *     maps to and [96, 128)) may hold anything, NaN included: they are staged with their rows but no gradient depends on them.          */
 long sn_weight_grads_workspace_bytes(long slot_rows, int dtype);
+/* The plan sn_weight_grads runs for (slot_rows, dtype), for tests and tools (host only like the sn_layout_* entries: no device call, no
+ * allocation; argument checks and error codes of sn_weight_grads_workspace_bytes, SN_E_BADARG for max_probs < 0 or a null out_host with
+ * max_probs > 0).  Returns the number of problems (14) and writes, for the first max_probs of them in launch order, 9 int32:
+ *   { variant | flag bits (the `variant` of sn_dw_gemm's task record), m, n, ns, per, launch group, first task in group,
+ *     c_off / 256, b_off / 256 or -1 }
+ * -- problem q is the m x n contraction split into ns K-ranges [j per, min((j + 1) per, slot_rows)), run by tasks first + j of launch
+ * `group`, partial j at workspace byte c_off + j m n 4 (column sums: b_off + j m 4; -1 = none).  Coverage property: per % 16 == 0 and
+ * (ns - 1) per < slot_rows <= ns per, i.e. every point lies in exactly one range and no range is empty.                              */
+int sn_weight_grads_plan(long slot_rows, int dtype, int32_t* out_host, int max_probs);
 int sn_weight_grads(const void* acts, const float* emb, const void* g_acts, long slot_rows, int dtype, void* workspace,
                     float* const* grads_host_array_of_device_ptrs, int accumulate, void* stream);
 

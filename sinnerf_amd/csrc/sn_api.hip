@@ -43,6 +43,7 @@ int sn_mlp_backward_chain_bf16x3_classic_launch(const void* bblob, const float* 
                                                 long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
 int sn_dw_launch(const void* tasks, int n_tasks, hipStream_t stream);
 long sn_weight_grads_workspace_bytes_impl(long slot_rows, int dtype, int emb16);
+int sn_weight_grads_plan_impl(long slot_rows, int dtype, int emb16, int* out, int max_probs);
 int sn_weight_grads_launch(const void* acts, const float* emb, const void* G, long slot_rows, int dtype, int emb16, void* workspace,
                            float* const* grads, int accumulate, hipStream_t stream);
 int sn_generate_rays_launch(const float* c2w, int H, int W, float focal, float near, float far, int x0, int y0, int sx,
@@ -384,6 +385,18 @@ long sn_weight_grads_workspace_bytes(long slot_rows, int dtype) {
   if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16_STATE && dtype != SN_DTYPE_BF16X3) return SN_E_UNSUPPORTED;
   if (emb16 && dtype != SN_DTYPE_BF16_STATE) return SN_E_UNSUPPORTED;
   return sn_weight_grads_workspace_bytes_impl(slot_rows, dtype, emb16);
+}
+
+int sn_weight_grads_plan(long slot_rows, int dtype, int32_t* out_host, int max_probs) {
+  // the checks of sn_weight_grads_workspace_bytes, in its order
+  if (slot_rows < 16 || slot_rows % 16 != 0) return SN_E_BADSHAPE;
+  const int emb16 = (dtype & SN_DTYPE_EMB_BF16) ? 1 : 0;
+  dtype &= ~SN_DTYPE_EMB_BF16;
+  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16_STATE && dtype != SN_DTYPE_BF16X3) return SN_E_UNSUPPORTED;
+  if (emb16 && dtype != SN_DTYPE_BF16_STATE) return SN_E_UNSUPPORTED;
+  if (max_probs < 0 || (max_probs > 0 && !out_host)) return SN_E_BADARG;
+  static_assert(sizeof(int32_t) == sizeof(int), "plan records are int32");
+  return sn_weight_grads_plan_impl(slot_rows, dtype, emb16, reinterpret_cast<int*>(out_host), max_probs);
 }
 
 int sn_weight_grads(const void* acts, const float* emb, const void* g_acts, long slot_rows, int dtype, void* workspace,

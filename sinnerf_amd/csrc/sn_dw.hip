@@ -770,6 +770,25 @@ extern "C" long sn_weight_grads_workspace_bytes_impl(long slot_rows, int dtype, 
   return hp.bytes;
 }
 
+// host-only introspection (sn_weight_grads_plan): the plan sn_weight_grads_launch hands to its kernels for this (slot_rows, dtype),
+// SN_DW_PLAN_FIELDS int32 per problem in build_plan's order.  No device call, no allocation.
+extern "C" int sn_weight_grads_plan_impl(long slot_rows, int dtype, int emb16, int* out, int max_probs) {
+  if (emb16 && (dtype != 2 || !SN_DW_NARROW_ASM || narrow_compiler_scheduled())) return -4;
+  snd::HostPlan hp;
+  snd::build_plan(hp, nullptr, nullptr, nullptr, slot_rows, dtype, emb16 != 0);
+  constexpr int SN_DW_PLAN_FIELDS = 9;
+  for (int i = 0; i < hp.plan.n_probs && i < max_probs; ++i) {
+    const snd::Prob& q = hp.plan.p[i];
+    // every partial buffer is a whole number of 256-byte lines (m * n * 4 and, for the problems that are followed by another, m * 4)
+    if (hp.c_off[i] % 256 != 0 || (hp.b_off[i] >= 0 && hp.b_off[i] % 256 != 0)) return -2;
+    int* r = out + i * SN_DW_PLAN_FIELDS;
+    r[0] = q.variant; r[1] = q.m; r[2] = q.ldc; r[3] = q.ns; r[4] = q.per;
+    r[5] = hp.group[i]; r[6] = hp.first_in_group[i];
+    r[7] = (int)(hp.c_off[i] / 256); r[8] = hp.b_off[i] >= 0 ? (int)(hp.b_off[i] / 256) : -1;
+  }
+  return hp.plan.n_probs;
+}
+
 extern "C" int sn_weight_grads_launch(const void* acts, const float* emb, const void* G, long slot_rows, int dtype, int emb16,
                                       void* workspace, float* const* grads, int accumulate, hipStream_t stream) {
   using namespace snd;

@@ -101,6 +101,9 @@ def dw_tasks(acts, emb, G, bf16=False):
     """Host-built task table for the raw ``sn_dw_gemm`` entry (the low-level ABI the weight-gradient tests and tools/dw_time.py
     exercise; the product path uses ``sn_weight_grads``, whose plan is built inside the library): the 14 contractions
     dW = G^T X of a network, K-split over ~one workgroup per CU in proportion to their cost.
+    The split below is a STAND-IN for timing tools and for the tests that only need some valid task table: it restates the library's
+    cost model and is not kept in step with it.  Tests of correctness read the plan the kernels are really given, through
+    ``dw_plan`` below (``sn_weight_grads_plan``), and never this one.
     Returns (rows: list of 8-int64 task records, outs: [(key, partial dW, partial db)])."""
     import numpy as np
     import torch
@@ -181,4 +184,80 @@ def x3_state_to_fp32(state):
     """(10, rows, 256) bf16x3 state -> the fp32 state an SN_DTYPE_F32 kernel reads (slots 0..8 decoded, slot 9 as is)"""
     out = np.array(state, copy=True)
     out[:9] = x3_state_decode(state[:9])
+    return out
+
+
+# ---- the fused weight-gradient entry (sn_weight_grads): its plan as the library builds it, and an fp64 reference -----------------------
+DW_PLAN_FIELDS = ("variant", "m", "n", "ns", "per", "group", "first", "c_off", "b_off")
+
+
+def dw_plan(rows, code):
+    """The plan ``sn_weight_grads(rows, code)`` runs, read from the library (``sn_weight_grads_plan``, host only): a list of dicts, one
+    per problem in launch order, with DW_PLAN_FIELDS (c_off / b_off in BYTES, b_off None = no bias partial) -- or the negative error code."""
+    import ctypes
+    from sinnerf_amd import _lib
+    n = _lib.lib.sn_weight_grads_plan(rows, code, None, 0)
+    if n < 0:
+        return n
+    buf = (ctypes.c_int32 * (9 * n))()
+    assert _lib.lib.sn_weight_grads_plan(rows, code, buf, n) == n
+    out = []
+    for i in range(n):
+        d = dict(zip(DW_PLAN_FIELDS, buf[9 * i:9 * i + 9]))
+        d["c_off"] *= 256
+        d["b_off"] = None if d["b_off"] < 0 else d["b_off"] * 256
+        out.append(d)
+    return out
+
+
+def dw_range_chunks(q, rows):
+    """(chunks of the first K-range, chunks of the last K-range) of problem q of a plan over `rows` points"""
+    return min(q["per"], rows) // 16, (rows - (q["ns"] - 1) * q["per"]) // 16
+
+
+# row counts of the K-range edge sweep (tests/test_weight_grads_edges_gpu.py; its reach is asserted there and in tests/test_dw_plan_cpu.py)
+# 16 c rows: c <= 7 is ONE range of c chunks per problem (below, at and above the 3-, 6- and 12-chunk prologues; odd and 1..3 chunk tails),
+# larger c two or more ranges with a short last one.  While the K-split is capped at rows / 64 a range is 4..7 chunks long, so ranges of
+# EIGHT chunks only appear where the cost table's own split takes over: 183, 248 and 736 (bf16x3, 256 x 256) are the sizes that deliver them
+# in every launch group of every mode (searched with dw_edge_reach; the reach is asserted, so a retuned table that moves them fails loudly)
+DW_EDGE_SMALL_CHUNKS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 16, 17, 24, 25, 33, 47, 65, 129, 183, 248, 736)
+DW_EDGE_WRAP_ROWS = 16656             # the narrow problems' K-ranges are longer than their 16-deep LDS ring
+DW_EDGE_ROWS = tuple(16 * c for c in DW_EDGE_SMALL_CHUNKS) + (DW_EDGE_WRAP_ROWS,)
+
+
+def dw_edge_reach(code, rows_list=DW_EDGE_ROWS):
+    """What the sweep over rows_list reaches in mode `code`: {problem set: (chunk counts seen in a first range, ... in a last range)} for
+    the problems of each launch group and for the 256 x 256 (variant 0) problems, and the longest range of a narrow problem at
+    DW_EDGE_WRAP_ROWS, in chunks."""
+    reach, longest_narrow = {}, 0
+    for rows in rows_list:
+        for q in dw_plan(rows, code):
+            f, l = dw_range_chunks(q, rows)
+            for key in (("group", q["group"]),) + ((("variant0",),) if q["variant"] & 0xff == 0 else ()):
+                a, b = reach.setdefault(key, (set(), set()))
+                a.add(f); b.add(l)
+            if rows == DW_EDGE_WRAP_ROWS and q["variant"] & 0xff != 0:
+                longest_narrow = max(longest_narrow, f)
+    return reach, longest_narrow
+
+
+RAW_SHAPES = [(256, 63), (256,)] + [(256, 256), (256,)] * 3 + [(256, 319), (256,)] + [(256, 256), (256,)] * 3 + \
+             [(256, 256), (256,), (128, 283), (128,), (1, 256), (1,), (3, 128), (3,)]
+
+
+def weight_grads_reference(acts, emb, G):
+    """fp64 contractions dW = G^T X / db = sum G in the parameters' shapes (autograd of models/nerf.py:66-103)."""
+    import torch
+    A, E, Gd = acts.double(), emb.double(), G.double()
+    out = []
+    for i in range(8):
+        x = E[:, :63] if i == 0 else A[i - 1]
+        if i == 4:
+            x = torch.cat([E[:, :63], A[3]], 1)                               # nerf.py:133
+        out += [Gd[i].T @ x, Gd[i].sum(0)]
+    out += [Gd[8].T @ A[7], Gd[8].sum(0)]
+    gd = Gd[9][:, :128]
+    out += [gd.T @ torch.cat([A[8], E[:, 64:91]], 1), gd.sum(0)]              # nerf.py:142
+    gh = Gd[9][:, 128:132]                                                    # [g_rgb(3), g_sigma(1)]
+    out += [gh[:, 3:4].T @ A[7], gh[:, 3:4].sum(0), gh[:, :3].T @ A[9][:, :128], gh[:, :3].sum(0)]
     return out

@@ -146,25 +146,7 @@ def test_losses_empty_batch_and_device_guard():
 
 
 # ------------------------------------------------------------------------------------------- fused weight-gradient entry
-_RAW_SHAPES = [(256, 63), (256,)] + [(256, 256), (256,)] * 3 + [(256, 319), (256,)] + [(256, 256), (256,)] * 3 + \
-              [(256, 256), (256,), (128, 283), (128,), (1, 256), (1,), (3, 128), (3,)]
-
-
-def _weight_grads_reference(acts, emb, G):
-    """fp64 contractions dW = G^T X / db = sum G in the parameters' shapes (autograd of models/nerf.py:66-103)."""
-    A, E, Gd = acts.double(), emb.double(), G.double()
-    out = []
-    for i in range(8):
-        x = E[:, :63] if i == 0 else A[i - 1]
-        if i == 4:
-            x = torch.cat([E[:, :63], A[3]], 1)                               # nerf.py:133
-        out += [Gd[i].T @ x, Gd[i].sum(0)]
-    out += [Gd[8].T @ A[7], Gd[8].sum(0)]
-    gd = Gd[9][:, :128]
-    out += [gd.T @ torch.cat([A[8], E[:, 64:91]], 1), gd.sum(0)]              # nerf.py:142
-    gh = Gd[9][:, 128:132]                                                    # [g_rgb(3), g_sigma(1)]
-    out += [gh[:, 3:4].T @ A[7], gh[:, 3:4].sum(0), gh[:, :3].T @ A[9][:, :128], gh[:, :3].sum(0)]
-    return out
+from tests.helpers import RAW_SHAPES as _RAW_SHAPES, weight_grads_reference as _weight_grads_reference      # noqa: E402
 
 
 @pytest.mark.parametrize("mode", ["fp32", "bf16", "bf16_state"])
