@@ -70,12 +70,25 @@ extern "C" {
 #define SN_FLAG_BF16_COMPILER_SCHEDULED 2
 /* bit 2: dtype SN_DTYPE_F32 only -- run the round-1..5 inference kernel (csrc/sn_mlp_fwd.hip: weights through an LDS ring filled by
  * LDS-DMA, one barrier per slab) instead of the round-6 one (csrc/sn_mlp_fwd_f32g.hip: A fragments straight from L2 into a register
- * ring, no VALU instruction in the trunk, no barrier); bit-identical results, kept for A/B timing.  Also honoured by
+ * ring, no VALU instruction in the trunk, no barrier); bit-identical results for non-NaN activations (the round-6 kernels take the
+ * ReLU as ds_max_i32 against 0, which turns a negative NaN into 0 and keeps a positive one, where v_max_f32 gives 0 for both -- the
+ * same caveat holds for SN_DTYPE_F32 | SN_DTYPE_COMPILER_SCHEDULED above); kept for A/B timing.  Also honoured by
  * sn_mlp_forward_embedded. */
 #define SN_FLAG_F32_LDS_RING 4
 
 int sn_abi_version(void);
 const char* sn_error_string(int code);
+
+/* kernel routing introspection (host only like the sn_layout_* entries: no device call, no allocation; additive within ABI 5; used by
+ * tests/test_api_routing_cpu.py).  The launcher the MLP entry `entry` hands (dtype, flags, sigma_only, n_points) to, as its symbol
+ * name without "_launch" (e.g. "sn_mlp_forward_bf16_v3_classic"), or NULL where that entry refuses the dtype with SN_E_UNSUPPORTED.
+ * `flags` and `sigma_only` count for the two inference entries only, `n_points` for the training ones. */
+#define SN_ROUTE_FORWARD 0          /* sn_mlp_forward */
+#define SN_ROUTE_FORWARD_EMBEDDED 1 /* sn_mlp_forward_embedded */
+#define SN_ROUTE_TRAIN 2            /* sn_mlp_forward_train */
+#define SN_ROUTE_TRAIN_EMBEDDED 3   /* sn_mlp_forward_train_embedded */
+#define SN_ROUTE_CHAIN 4            /* sn_mlp_backward_chain */
+const char* sn_mlp_route(int entry, int dtype, int flags, int sigma_only, long n_points);
 
 /* layout introspection (host only; mirrors csrc/sn_layout.h -- used by the CPU layout tests) */
 int sn_layout_xyz_slot_col(int lane_half, int slot); /* reference Embedding(3,10) column, -1 = zero pad */

@@ -102,8 +102,8 @@ def fp16_round(a):
 
 class fp16_operands(bf16_operands):
     """Context manager: as ``bf16_operands`` with fp16-rounded operands (11 significand bits instead of 8; v_mfma_f32_32x32x16_f16
-    runs at the bf16 rate on gfx950).  ORACLE-SIDE EXPERIMENT ONLY: no kernel implements it; tools/precision_probe.py
-    prints what it would buy on the trained-weight fixtures."""
+    runs at the bf16 rate on gfx950).  The arithmetic of SN_DTYPE_F16 (inference: sn_mlp_forward, sn_mlp_forward_embedded);
+    tools/precision_probe.py prints what it buys on the trained-weight fixtures."""
 
     def __enter__(self):
         global _OPERAND_ROUND

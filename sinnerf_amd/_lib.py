@@ -30,6 +30,7 @@ _long, _int, _float = ctypes.c_long, ctypes.c_int, ctypes.c_float
 SIGNATURES = {
     "sn_abi_version": (_int, []),
     "sn_error_string": (ctypes.c_char_p, [_int]),
+    "sn_mlp_route": (ctypes.c_char_p, [_int, _int, _int, _int, _long]),
     "sn_layout_xyz_slot_col": (_int, [_int, _int]),
     "sn_layout_dir_slot_col": (_int, [_int, _int]),
     "sn_layout_slab_k": (_int, [_int]),

@@ -2,120 +2,8 @@
 #include <hip/hip_fp16.h>
 #include "../../include/sinnerf_hip.h"
 #include "sn_device.h"
+#include "sn_launch.h"
 #include "sn_layout.h"
-
-extern "C" {
-int sn_mlp_forward_f32_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld,
-                              int sigma_only, int input_mode, float* out, float* acts, float* emb,
-                              long slot_rows, hipStream_t stream);
-int sn_mlp_forward_f32g_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld, int sigma_only,
-                               int input_mode, float* out, float* acts, float* emb, long slot_rows, hipStream_t stream);
-int sn_mlp_forward_f32g_classic_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld, int sigma_only,
-                                       int input_mode, float* out, float* acts, float* emb, long slot_rows, hipStream_t stream);
-int sn_mlp_forward_f32g_store_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld, int sigma_only,
-                                     int input_mode, float* out, float* acts, float* emb, long slot_rows, hipStream_t stream);
-int sn_mlp_forward_f32g_store_classic_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld, int sigma_only,
-                                             int input_mode, float* out, float* acts, float* emb, long slot_rows, hipStream_t stream);
-int sn_mlp_forward_f32_classic_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld,
-                              int sigma_only, int input_mode, float* out, float* acts, float* emb,
-                              long slot_rows, hipStream_t stream);
-int sn_mlp_backward_chain_f32_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                     long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_mlp_backward_chain_f32_classic_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                     long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_mlp_backward_chain_f32g_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw, long n_points,
-                                      long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_mlp_backward_chain_f32g_classic_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                              long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_mlp_backward_chain_bf16_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                      long n_points, long slot_rows, float* G, float* g_out, int state_bf16,
-                                      hipStream_t stream);
-int sn_mlp_backward_chain_bf16_classic_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                      long n_points, long slot_rows, float* G, float* g_out, int state_bf16,
-                                      hipStream_t stream);
-int sn_mlp_backward_chain_bf16x3_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                        long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_mlp_backward_chain_bf16x3_t_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                          long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_mlp_backward_chain_bf16x3_t_classic_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                                  long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_mlp_backward_chain_bf16x3_classic_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                                long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_dw_launch(const void* tasks, int n_tasks, hipStream_t stream);
-long sn_weight_grads_workspace_bytes_impl(long slot_rows, int dtype, int emb16);
-int sn_weight_grads_plan_impl(long slot_rows, int dtype, int emb16, int* out, int max_probs);
-int sn_weight_grads_launch(const void* acts, const float* emb, const void* G, long slot_rows, int dtype, int emb16, void* workspace,
-                           float* const* grads, int accumulate, hipStream_t stream);
-int sn_generate_rays_launch(const float* c2w, int H, int W, float focal, float near, float far, int x0, int y0, int sx,
-                            int sy, int pw, int ph, float* rays, hipStream_t stream);
-int sn_adam_step_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
-                        float wd, int step, hipStream_t stream);
-long sn_render_loss_workspace_bytes_impl();
-int sn_render_loss_launch(const float* rgb_c, const float* rgb_f, const float* depth_c, const float* depth_f,
-                          const float* rgb_gt, const float* depth_gt, const unsigned char* mask, int mask_mode, long n,
-                          float w_rgb, float w_depth, float* g_rgb_c, float* g_rgb_f, float* g_depth_c, float* g_depth_f,
-                          void* workspace, float* out, hipStream_t stream);
-int sn_mlp_forward_bf16_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld,
-                               int sigma_only, int input_mode, float* out, float* acts, float* emb, long slot_rows,
-                               int state_bf16, hipStream_t stream);
-int sn_mlp_forward_bf16_classic_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld,
-                               int sigma_only, int input_mode, float* out, float* acts, float* emb, long slot_rows,
-                               int state_bf16, hipStream_t stream);
-// ... the fp16-operand pass of the two bf16 inference kernels (SN_DTYPE_F16, -DSN_OPERAND_F16)
-int sn_mlp_forward_bf16_f16_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld,
-                               int sigma_only, int input_mode, float* out, float* acts, float* emb, long slot_rows,
-                               int state_bf16, hipStream_t stream);
-int sn_mlp_forward_bf16_f16_classic_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld,
-                               int sigma_only, int input_mode, float* out, float* acts, float* emb, long slot_rows,
-                               int state_bf16, hipStream_t stream);
-int sn_mlp_forward_bf16_v3_f16_launch(const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples,
-                                  float* out, hipStream_t stream);
-int sn_mlp_forward_bf16_v3_f16_classic_launch(const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples,
-                                  float* out, hipStream_t stream);
-int sn_mlp_forward_bf16x3_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld, int sigma_only,
-                                 int input_mode, float* out, float* acts, float* emb, long slot_rows, hipStream_t stream);
-int sn_mlp_forward_bf16x3_classic_launch(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld,
-                                         int sigma_only, int input_mode, float* out, float* acts, float* emb, long slot_rows,
-                                         hipStream_t stream);
-int sn_mlp_forward_bf16x3_t_launch(const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples, float* out,
-                                   float* acts, float* emb, long slot_rows, hipStream_t stream);
-int sn_mlp_forward_bf16x3_t_classic_launch(const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples, float* out,
-                                           float* acts, float* emb, long slot_rows, hipStream_t stream);
-int sn_mlp_forward_bf16_v3_launch(const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples,
-                                  float* out, hipStream_t stream);
-int sn_mlp_forward_bf16_v3_classic_launch(const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples,
-                                  float* out, hipStream_t stream);
-int sn_mlp_forward_bf16_t_launch(const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples, float* out,
-                                 float* acts, float* emb, long slot_rows, int emb16, hipStream_t stream);
-int sn_mlp_forward_bf16_t_classic_launch(const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples,
-                                         float* out, float* acts, float* emb, long slot_rows, int emb16, hipStream_t stream);
-int sn_mlp_backward_chain_bf16_t_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw, long n_points,
-                                        long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_mlp_backward_chain_bf16_t_classic_launch(const void* bblob, const float* acts, const float* out_raw, const float* g_raw,
-                                                long n_points, long slot_rows, float* G, float* g_out, hipStream_t stream);
-int sn_composite_backward_launch(const float* raw, const float* z_vals, const float* rays, const float* noise,
-                                 float noise_std, long n_rays, int n_samples, int white_back, const float* g_rgb,
-                                 const float* g_depth, const float* g_w, float* g_raw, hipStream_t stream);
-int sn_composite_backward_rays_launch(const float* raw, const float* z_vals, const float* rays, const float* noise,
-                                      float noise_std, long n_rays, int n_samples, int white_back, const float* g_rgb,
-                                      const float* g_depth, const float* g_w, float* g_raw, float* g_rays, hipStream_t stream);
-long sn_ray_grads_workspace_bytes_impl(long n_rays, int n_samples);
-int sn_ray_grads_launch(const float* w1, const float* w5, const float* wdir, int layout, const void* g_acts, long slot_rows,
-                        const float* rays, const float* z_vals, long n_rays, int n_samples, void* workspace, float* g_rays,
-                        hipStream_t stream);
-long sn_generate_rays_backward_workspace_bytes_impl();
-int sn_generate_rays_backward_launch(const float* g_rays, int H, int W, float focal, int x0, int y0, int sx, int sy, int pw,
-                                     int ph, void* workspace, float* g_c2w, hipStream_t stream);
-int sn_sample_coarse_launch(const float* rays, long n_rays, int n_samples, int use_disp, float perturb,
-                            const float* perturb_rand, float* z_out, hipStream_t stream);
-int sn_composite_forward_launch(const float* raw, int has_rgb, const float* z_vals, const float* rays,
-                                const float* noise, float noise_std, long n_rays, int n_samples, int white_back,
-                                float* rgb, float* depth, float* weights, hipStream_t stream);
-int sn_sample_pdf_launch(const float* z_vals, const float* weights, const float* u, long n_rays, int n_samples,
-                         int n_importance, float* z_fine, float* z_merged, hipStream_t stream);
-int sn_sample_pdf_bins_launch(const float* bins, const float* weights, const float* u, long n_rays, int n_bins,
-                              int n_importance, float eps, float* samples, hipStream_t stream);
-}
 
 namespace {
 struct RawPtrs { const float* p[snl::N_RAW]; };
@@ -147,6 +35,126 @@ pack_kernel(RawPtrs raw, const snl::PackEntry* __restrict__ table, long n, char*
     else *reinterpret_cast<unsigned short*>(blob + e.dst) = f32_to_bf16_rne(v);
   }
 }
+
+// ---- the `dtype` argument: a base code with flag bits OR-ed in.  Every entry names the bits and the bases it accepts; a bit it does
+// not accept stays in the base code and is refused with it.
+constexpr unsigned bit(int base) { return 1u << base; }
+constexpr unsigned PACKABLE = bit(SN_DTYPE_F32) | bit(SN_DTYPE_BF16) | bit(SN_DTYPE_BF16X3) | bit(SN_DTYPE_F16);       // = the inference set
+constexpr unsigned TRAINABLE = bit(SN_DTYPE_F32) | bit(SN_DTYPE_BF16) | bit(SN_DTYPE_BF16_STATE) | bit(SN_DTYPE_BF16X3);
+struct Dtype { int base, bits; };
+bool parse_dtype(int dtype, int accepted_bits, unsigned accepted_bases, Dtype* d) {
+  d->bits = dtype & accepted_bits;
+  d->base = dtype & ~accepted_bits;
+  return d->base >= 0 && d->base < 32 && (accepted_bases >> d->base & 1u);
+}
+// points per tile of the MLP kernels of an arithmetic: the training state is stored / written in whole tiles
+constexpr long tile_rows(int base) { return (base == SN_DTYPE_F32 || base == SN_DTYPE_BF16X3) ? 128 : 256; }
+bool holds_whole_tiles(long slot_rows, long n_points, int base) {
+  const long tile = tile_rows(base);
+  return slot_rows >= (n_points + tile - 1) / tile * tile;
+}
+bool packable(int dtype) { Dtype d; return parse_dtype(dtype, 0, PACKABLE, &d); }
+// sn_weight_grads and its two queries: SN_DTYPE_EMB_BF16 is the only bit, refused where the kernels cannot read that form (sn_launch.h)
+int parse_dw_dtype(int dtype, Dtype* d) {
+  if (!parse_dtype(dtype, SN_DTYPE_EMB_BF16, TRAINABLE, d)) return SN_E_UNSUPPORTED;
+  d->bits = d->bits ? 1 : 0;                     // = the emb16 argument of the *_impl / *_launch functions
+  return snh::emb16_refused(d->base, d->bits) ? SN_E_UNSUPPORTED : 0;
+}
+
+// ---- which kernel runs: a pure function of the arguments (no HIP call), exported as sn_mlp_route for the CPU routing test.
+// The two compilation passes of the MLP kernels (sn_device.h): SN_DTYPE_CLASSIC_HEADS in `dtype` selects the ReLU / Sigmoid pass; a
+// sigma-only evaluation never reaches the heads and always runs the main pass.
+#define SN_HEADS(classic, name) ((classic) ? name##_classic_launch : name##_launch)
+#define SN_MLP_LAUNCHERS(X)                                                                                                          \
+  X(sn_mlp_forward_f32) X(sn_mlp_forward_f32g) X(sn_mlp_forward_f32g_store) X(sn_mlp_forward_bf16) X(sn_mlp_forward_bf16_f16)        \
+  X(sn_mlp_forward_bf16_v3) X(sn_mlp_forward_bf16_v3_f16) X(sn_mlp_forward_bf16_t) X(sn_mlp_forward_bf16x3) X(sn_mlp_forward_bf16x3_t) \
+  X(sn_mlp_backward_chain_f32) X(sn_mlp_backward_chain_f32g) X(sn_mlp_backward_chain_bf16) X(sn_mlp_backward_chain_bf16_t)           \
+  X(sn_mlp_backward_chain_bf16x3) X(sn_mlp_backward_chain_bf16x3_t)
+#define SN_X(name) K_##name,
+enum Launcher { SN_MLP_LAUNCHERS(SN_X) K_NONE };
+#undef SN_X
+#define SN_X(name) {#name, #name "_classic"},
+const char* const LAUNCHER_NAMES[][2] = {SN_MLP_LAUNCHERS(SN_X)};
+#undef SN_X
+struct Route { Launcher k; bool classic; };
+
+enum Family { FORWARD, TRAIN, CHAIN };
+struct Entry { Family family; int input_mode, dtype_bits; unsigned bases; };
+constexpr Entry ENTRIES[] = {
+    /* SN_ROUTE_FORWARD          */ {FORWARD, 0, SN_DTYPE_CLASSIC_HEADS, PACKABLE},
+    /* SN_ROUTE_FORWARD_EMBEDDED */ {FORWARD, 1, SN_DTYPE_CLASSIC_HEADS, PACKABLE},
+    /* SN_ROUTE_TRAIN            */ {TRAIN, 0, SN_DTYPE_CLASSIC_HEADS | SN_DTYPE_COMPILER_SCHEDULED | SN_DTYPE_EMB_BF16, TRAINABLE},
+    // (mixed precision keeps bf16 state: no SN_DTYPE_BF16; no previous-generation bit)
+    /* SN_ROUTE_TRAIN_EMBEDDED   */ {TRAIN, 1, SN_DTYPE_CLASSIC_HEADS, TRAINABLE & ~bit(SN_DTYPE_BF16)},
+    /* SN_ROUTE_CHAIN            */ {CHAIN, 0, SN_DTYPE_CLASSIC_HEADS | SN_DTYPE_COMPILER_SCHEDULED, TRAINABLE},
+};
+bool accepts(int entry, int dtype, Dtype* d) { return parse_dtype(dtype, ENTRIES[entry].dtype_bits, ENTRIES[entry].bases, d); }
+constexpr int FORWARD_FLAGS = SN_FLAG_BF16_COMPILER_SCHEDULED | SN_FLAG_F32_LDS_RING;      // the `flags` bits of the inference entries
+
+// base: an accepted base code; bits: the dtype's flag bits | the SN_FLAG_* bits of `flags` (disjoint values).  K_NONE = refused.
+Route route(Family family, int base, int bits, int sigma_only, int input_mode, long n_points) {
+  const bool previous = bits & SN_DTYPE_COMPILER_SCHEDULED;
+  if (family == FORWARD) {
+    const bool classic = (bits & SN_DTYPE_CLASSIC_HEADS) && !sigma_only;
+    // the hand-scheduled bf16 / fp16 kernel takes (rays, z_vals) and has no sigma-only form
+    const bool hand = input_mode == 0 && !sigma_only && !(bits & SN_FLAG_BF16_COMPILER_SCHEDULED);
+    switch (base) {
+      case SN_DTYPE_BF16X3: return {K_sn_mlp_forward_bf16x3, classic};     // fp32-level accuracy on the bf16 MFMA: 3-term split
+      case SN_DTYPE_F16: return {hand ? K_sn_mlp_forward_bf16_v3_f16 : K_sn_mlp_forward_bf16_f16, classic};    // fp16 operands, bf16 streams
+      case SN_DTYPE_BF16: return {hand ? K_sn_mlp_forward_bf16_v3 : K_sn_mlp_forward_bf16, classic};
+      // round 6: fragments straight from L2, VALU-free trunk (csrc/sn_mlp_fwd_f32g.hip)
+      case SN_DTYPE_F32: return {(bits & SN_FLAG_F32_LDS_RING) ? K_sn_mlp_forward_f32 : K_sn_mlp_forward_f32g, classic};
+    }
+    return {K_NONE, false};
+  }
+  const bool classic = bits & SN_DTYPE_CLASSIC_HEADS;
+  // the generated instruction streams (sn_mlp_*_t.hip: the same bits as the compiler-scheduled kernels) index points with 32 bits
+  const bool generated = !previous && input_mode == 0 && n_points < (1l << 31) - 256;
+  Launcher k = K_NONE;
+  if (family == TRAIN) {
+    switch (base) {
+      case SN_DTYPE_BF16X3: k = generated ? K_sn_mlp_forward_bf16x3_t : K_sn_mlp_forward_bf16x3; break;
+      case SN_DTYPE_BF16_STATE: k = generated ? K_sn_mlp_forward_bf16_t : K_sn_mlp_forward_bf16; break;
+      case SN_DTYPE_BF16: k = K_sn_mlp_forward_bf16; break;
+      // round 6: the fragments-from-L2 kernel in store mode (csrc/sn_mlp_fwd_f32g.hip): the same state
+      case SN_DTYPE_F32: k = previous ? K_sn_mlp_forward_f32 : K_sn_mlp_forward_f32g_store; break;
+    }
+    // only the hand-scheduled kernel writes the bf16 form of emb
+    if ((bits & SN_DTYPE_EMB_BF16) && k != K_sn_mlp_forward_bf16_t) k = K_NONE;
+  } else {
+    switch (base) {
+      case SN_DTYPE_BF16X3: k = generated ? K_sn_mlp_backward_chain_bf16x3_t : K_sn_mlp_backward_chain_bf16x3; break;
+      case SN_DTYPE_BF16_STATE: k = generated ? K_sn_mlp_backward_chain_bf16_t : K_sn_mlp_backward_chain_bf16; break;
+      case SN_DTYPE_BF16: k = K_sn_mlp_backward_chain_bf16; break;
+      // round 6: the fragments-from-L2 chain (csrc/sn_mlp_bwd_f32g.hip): the same bits
+      case SN_DTYPE_F32: k = previous ? K_sn_mlp_backward_chain_f32 : K_sn_mlp_backward_chain_f32g; break;
+    }
+  }
+  return {k, classic};
+}
+
+// the forward launchers, inference (acts = emb = nullptr, slot_rows = 0) and training
+int launch_forward(Route r, int base, const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld, int sigma_only,
+                   int input_mode, float* out, float* acts, float* emb, long slot_rows, int emb16, hipStream_t stream) {
+  const int state_bf16 = base == SN_DTYPE_BF16_STATE;
+#define SN_FWD(name) return SN_HEADS(r.classic, name)(blob, in0, in1, n_points, s_or_ld, sigma_only, input_mode, out, acts, emb, slot_rows
+  switch (r.k) {
+    case K_sn_mlp_forward_f32: SN_FWD(sn_mlp_forward_f32), stream);
+    case K_sn_mlp_forward_f32g: SN_FWD(sn_mlp_forward_f32g), stream);
+    case K_sn_mlp_forward_f32g_store: SN_FWD(sn_mlp_forward_f32g_store), stream);
+    case K_sn_mlp_forward_bf16x3: SN_FWD(sn_mlp_forward_bf16x3), stream);
+    case K_sn_mlp_forward_bf16: SN_FWD(sn_mlp_forward_bf16), state_bf16, stream);
+    case K_sn_mlp_forward_bf16_f16: SN_FWD(sn_mlp_forward_bf16_f16), state_bf16, stream);
+#undef SN_FWD
+    case K_sn_mlp_forward_bf16_v3: return SN_HEADS(r.classic, sn_mlp_forward_bf16_v3)(blob, in0, in1, n_points, s_or_ld, out, stream);
+    case K_sn_mlp_forward_bf16_v3_f16: return SN_HEADS(r.classic, sn_mlp_forward_bf16_v3_f16)(blob, in0, in1, n_points, s_or_ld, out, stream);
+    case K_sn_mlp_forward_bf16_t:
+      return SN_HEADS(r.classic, sn_mlp_forward_bf16_t)(blob, in0, in1, n_points, s_or_ld, out, acts, emb, slot_rows, emb16, stream);
+    case K_sn_mlp_forward_bf16x3_t:
+      return SN_HEADS(r.classic, sn_mlp_forward_bf16x3_t)(blob, in0, in1, n_points, s_or_ld, out, acts, emb, slot_rows, stream);
+    default: return SN_E_UNSUPPORTED;
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -172,17 +180,17 @@ const char* sn_error_string(int code) {
 }
 
 long sn_packed_weights_bytes(int dtype) {
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16X3 && dtype != SN_DTYPE_F16) return SN_E_UNSUPPORTED;
+  if (!packable(dtype)) return SN_E_UNSUPPORTED;
   return snl::blob_bytes(dtype);
 }
 long sn_pack_table_entries(void) { return snl::table_entries(); }
 long sn_pack_table_entries_dtype(int dtype) {
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16X3 && dtype != SN_DTYPE_F16) return SN_E_UNSUPPORTED;
+  if (!packable(dtype)) return SN_E_UNSUPPORTED;
   return snl::table_entries_dt(dtype);
 }
 
 int sn_build_pack_table(int dtype, int32_t* table_host) {
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16X3 && dtype != SN_DTYPE_F16) return SN_E_UNSUPPORTED;
+  if (!packable(dtype)) return SN_E_UNSUPPORTED;
   if (!table_host) return SN_E_BADARG;
   snl::build_pack_table(dtype, reinterpret_cast<snl::PackEntry*>(table_host));
   return 0;
@@ -213,7 +221,7 @@ int sn_build_pack_table_bwd_bf16x3(int32_t* table_host) {
 }
 
 int sn_pack_weights(const float* const* raw, const int32_t* table, long n_entries, void* blob, int dtype, void* stream) {
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16X3 && dtype != SN_DTYPE_F16) return SN_E_UNSUPPORTED;
+  if (!packable(dtype)) return SN_E_UNSUPPORTED;
   if (!raw || !table || !blob || n_entries <= 0) return SN_E_BADARG;
   RawPtrs rp;
   for (int i = 0; i < snl::N_RAW; ++i) {
@@ -231,69 +239,50 @@ int sn_sample_coarse(const float* rays, long n_rays, int n_samples, int use_disp
   return sn_sample_coarse_launch(rays, n_rays, n_samples, use_disp, perturb, perturb_rand, z_vals, (hipStream_t)stream);
 }
 
-// the two compilation passes of the MLP kernels (sn_device.h): SN_DTYPE_CLASSIC_HEADS in `dtype` selects the ReLU / Sigmoid
-// pass; a sigma-only evaluation never reaches the heads and always runs the main pass
-#define SN_HEADS(classic, name) ((classic) ? name##_classic_launch : name##_launch)
+const char* sn_mlp_route(int entry, int dtype, int flags, int sigma_only, long n_points) {
+  if (entry < 0 || entry >= (int)(sizeof(ENTRIES) / sizeof(ENTRIES[0]))) return nullptr;
+  const Entry& e = ENTRIES[entry];
+  Dtype d;
+  if (!accepts(entry, dtype, &d)) return nullptr;
+  const bool fwd = e.family == FORWARD;
+  const Route r = route(e.family, d.base, d.bits | (fwd ? flags & FORWARD_FLAGS : 0), fwd && sigma_only, e.input_mode, n_points);
+  return r.k == K_NONE ? nullptr : LAUNCHER_NAMES[r.k][r.classic];
+}
 
 int sn_mlp_forward(const void* blob, int dtype, const float* rays, const float* z_vals, long n_rays, int n_samples,
                    int sigma_only, int flags, float* out, void* stream) {
   if (!blob || !rays || !z_vals || !out || n_rays < 0 || n_samples < 1) return SN_E_BADARG;
-  const bool classic = (dtype & SN_DTYPE_CLASSIC_HEADS) && !sigma_only;
-  dtype &= ~SN_DTYPE_CLASSIC_HEADS;
-  if (dtype == SN_DTYPE_BF16X3)                  // fp32-level accuracy on the bf16 MFMA: 3-term split (csrc/sn_mlp_fwd_bf16x3.hip)
-    return SN_HEADS(classic, sn_mlp_forward_bf16x3)(blob, rays, z_vals, n_rays * (long)n_samples, n_samples, sigma_only, 0, out,
-                                                    nullptr, nullptr, 0, (hipStream_t)stream);
-  if (dtype == SN_DTYPE_F16) {                   // fp16 operands on the bf16 kernels' instruction streams (round 6; inference only)
-    if (!sigma_only && !(flags & SN_FLAG_BF16_COMPILER_SCHEDULED))
-      return (classic ? sn_mlp_forward_bf16_v3_f16_classic_launch : sn_mlp_forward_bf16_v3_f16_launch)(
-          blob, rays, z_vals, n_rays * (long)n_samples, n_samples, out, (hipStream_t)stream);
-    return (classic ? sn_mlp_forward_bf16_f16_classic_launch : sn_mlp_forward_bf16_f16_launch)(
-        blob, rays, z_vals, n_rays * (long)n_samples, n_samples, sigma_only, 0, out, nullptr, nullptr, 0, 0, (hipStream_t)stream);
-  }
-  if (dtype == SN_DTYPE_BF16 && !sigma_only && !(flags & SN_FLAG_BF16_COMPILER_SCHEDULED))     // the hand-scheduled kernel
-    return SN_HEADS(classic, sn_mlp_forward_bf16_v3)(blob, rays, z_vals, n_rays * (long)n_samples, n_samples, out, (hipStream_t)stream);
-  if (dtype == SN_DTYPE_BF16)
-    return SN_HEADS(classic, sn_mlp_forward_bf16)(blob, rays, z_vals, n_rays * (long)n_samples, n_samples, sigma_only, 0, out, nullptr,
-                                                  nullptr, 0, 0, (hipStream_t)stream);
-  if (dtype != SN_DTYPE_F32) return SN_E_UNSUPPORTED;
-  if (!(flags & SN_FLAG_F32_LDS_RING))           // round 6: fragments straight from L2, VALU-free trunk (csrc/sn_mlp_fwd_f32g.hip)
-    return SN_HEADS(classic, sn_mlp_forward_f32g)(blob, rays, z_vals, n_rays * (long)n_samples, n_samples, sigma_only, 0, out,
-                                                  nullptr, nullptr, 0, (hipStream_t)stream);
-  return SN_HEADS(classic, sn_mlp_forward_f32)(blob, rays, z_vals, n_rays * (long)n_samples, n_samples, sigma_only, 0,
-                                               out, nullptr, nullptr, 0, (hipStream_t)stream);
+  Dtype d;
+  if (!accepts(SN_ROUTE_FORWARD, dtype, &d)) return SN_E_UNSUPPORTED;
+  return launch_forward(route(FORWARD, d.base, d.bits | (flags & FORWARD_FLAGS), sigma_only, 0, 0), d.base, blob, rays, z_vals,
+                        n_rays * (long)n_samples, n_samples, sigma_only, 0, out, nullptr, nullptr, 0, 0, (hipStream_t)stream);
 }
 
+int sn_mlp_forward_embedded(const void* blob, int dtype, const float* x, long n_rows, int ld, int sigma_only,
+                            int flags, float* out, void* stream) {
+  if (!blob || !x || !out || n_rows < 0) return SN_E_BADARG;
+  if (ld < (sigma_only ? 63 : 90)) return SN_E_BADSHAPE;
+  Dtype d;
+  if (!accepts(SN_ROUTE_FORWARD_EMBEDDED, dtype, &d)) return SN_E_UNSUPPORTED;
+  return launch_forward(route(FORWARD, d.base, d.bits | (flags & FORWARD_FLAGS), sigma_only, 1, 0), d.base, blob, x, nullptr, n_rows, ld,
+                        sigma_only, 1, out, nullptr, nullptr, 0, 0, (hipStream_t)stream);
+}
+
+// SN_DTYPE_BF16X3: fp32-level forward on the bf16 MFMA.  Its training state is the "x3 state" of sn_layout.h -- slots 0..8 hold (hi, lo)
+// bf16 PAIRS in the bytes of an fp32 row, slot 9 fp32 values + ReLU sign words -- NOT the array SN_DTYPE_F32 writes: only the
+// SN_DTYPE_BF16X3 forms of sn_mlp_backward_chain / sn_weight_grads read it (include/sinnerf_hip.h "pairing rule")
 int sn_mlp_forward_train(const void* blob, int dtype, const float* rays, const float* z_vals, long n_rays, int n_samples,
                          float* out, float* acts, float* emb, long slot_rows, void* stream) {
   if (!blob || !rays || !z_vals || !out || !acts || !emb || n_rays < 0 || n_samples < 1) return SN_E_BADARG;
-  const bool classic = dtype & SN_DTYPE_CLASSIC_HEADS;
-  const bool compiler_scheduled = dtype & SN_DTYPE_COMPILER_SCHEDULED;
-  const int emb16 = (dtype & SN_DTYPE_EMB_BF16) ? 1 : 0;
-  dtype &= ~(SN_DTYPE_CLASSIC_HEADS | SN_DTYPE_COMPILER_SCHEDULED | SN_DTYPE_EMB_BF16);
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16_STATE && dtype != SN_DTYPE_BF16X3) return SN_E_UNSUPPORTED;
+  Dtype d;
+  if (!accepts(SN_ROUTE_TRAIN, dtype, &d)) return SN_E_UNSUPPORTED;
   const long n_points = n_rays * (long)n_samples;
-  const long tile = (dtype == SN_DTYPE_F32 || dtype == SN_DTYPE_BF16X3) ? 128 : 256;      // whole point tiles are stored
-  if (slot_rows < (n_points + tile - 1) / tile * tile) return SN_E_BADSHAPE;
-  const bool hand = dtype == SN_DTYPE_BF16_STATE && !compiler_scheduled && n_points < (1l << 31) - 256;   // the hand-scheduled kernel
-  if (emb16 && !hand) return SN_E_UNSUPPORTED;                               // (the only one that writes the bf16 form of emb)
-  // fp32-level forward on the bf16 MFMA.  Its training state is the "x3 state" of sn_layout.h -- slots 0..8 hold (hi, lo) bf16 PAIRS in
-  // the bytes of an fp32 row, slot 9 fp32 values + ReLU sign words -- NOT the array SN_DTYPE_F32 writes: only the SN_DTYPE_BF16X3 forms of
-  // sn_mlp_backward_chain / sn_weight_grads read it (include/sinnerf_hip.h "pairing rule")
-  if (dtype == SN_DTYPE_BF16X3) {
-    if (slot_rows % 128 != 0) return SN_E_BADSHAPE;           // whole 128-point tiles, as the header states
-    if (!compiler_scheduled && n_points < (1l << 31) - 256)  // the generated trunk (sn_mlp_fwd_bf16x3_t.hip): the same bits
-      return SN_HEADS(classic, sn_mlp_forward_bf16x3_t)(blob, rays, z_vals, n_points, n_samples, out, acts, emb, slot_rows, (hipStream_t)stream);
-    return SN_HEADS(classic, sn_mlp_forward_bf16x3)(blob, rays, z_vals, n_points, n_samples, 0, 0, out, acts, emb, slot_rows, (hipStream_t)stream);
-  }
-  if (hand)
-    return SN_HEADS(classic, sn_mlp_forward_bf16_t)(blob, rays, z_vals, n_points, n_samples, out, acts, emb, slot_rows, emb16, (hipStream_t)stream);
-  if (dtype != SN_DTYPE_F32)
-    return SN_HEADS(classic, sn_mlp_forward_bf16)(blob, rays, z_vals, n_points, n_samples, 0, 0, out, acts, emb, slot_rows,
-                                                  dtype == SN_DTYPE_BF16_STATE, (hipStream_t)stream);
-  if (!compiler_scheduled)                       // round 6: the fragments-from-L2 kernel in store mode (csrc/sn_mlp_fwd_f32g.hip): the same state
-    return SN_HEADS(classic, sn_mlp_forward_f32g_store)(blob, rays, z_vals, n_points, n_samples, 0, 0, out, acts, emb, slot_rows, (hipStream_t)stream);
-  return SN_HEADS(classic, sn_mlp_forward_f32)(blob, rays, z_vals, n_points, n_samples, 0, 0, out, acts, emb, slot_rows,
-                                               (hipStream_t)stream);
+  if (!holds_whole_tiles(slot_rows, n_points, d.base)) return SN_E_BADSHAPE;
+  const Route r = route(TRAIN, d.base, d.bits, 0, 0, n_points);
+  if (r.k == K_NONE) return SN_E_UNSUPPORTED;                                  // SN_DTYPE_EMB_BF16 without the kernel that writes it
+  if (d.base == SN_DTYPE_BF16X3 && slot_rows % 128 != 0) return SN_E_BADSHAPE;  // whole 128-point tiles, as the header states
+  return launch_forward(r, d.base, blob, rays, z_vals, n_points, n_samples, 0, 0, out, acts, emb, slot_rows,
+                        (d.bits & SN_DTYPE_EMB_BF16) ? 1 : 0, (hipStream_t)stream);
 }
 
 int sn_mlp_forward_train_embedded(const void* blob, int dtype, const float* x, long n_rows, int ld, float* out,
@@ -301,45 +290,34 @@ int sn_mlp_forward_train_embedded(const void* blob, int dtype, const float* x, l
   if (!blob || !x || !out || !acts || n_rows < 0) return SN_E_BADARG;
   float* emb = acts;                             // not written for pre-embedded rows (the kernels only need it non-null)
   if (ld < 90) return SN_E_BADSHAPE;
-  const bool classic = dtype & SN_DTYPE_CLASSIC_HEADS;
-  dtype &= ~SN_DTYPE_CLASSIC_HEADS;
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16_STATE && dtype != SN_DTYPE_BF16X3) return SN_E_UNSUPPORTED;   // mixed precision keeps bf16 state
-  const long tile = (dtype == SN_DTYPE_F32 || dtype == SN_DTYPE_BF16X3) ? 128 : 256;
-  if (slot_rows < (n_rows + tile - 1) / tile * tile) return SN_E_BADSHAPE;
-  if (dtype == SN_DTYPE_BF16X3)
-    return SN_HEADS(classic, sn_mlp_forward_bf16x3)(blob, x, nullptr, n_rows, ld, 0, 1, out, acts, emb, slot_rows, (hipStream_t)stream);
-  if (dtype != SN_DTYPE_F32)
-    return SN_HEADS(classic, sn_mlp_forward_bf16)(blob, x, nullptr, n_rows, ld, 0, 1, out, acts, emb, slot_rows,
-                                                  dtype == SN_DTYPE_BF16_STATE, (hipStream_t)stream);
-  return SN_HEADS(classic, sn_mlp_forward_f32g_store)(blob, x, nullptr, n_rows, ld, 0, 1, out, acts, emb, slot_rows, (hipStream_t)stream);
+  Dtype d;
+  if (!accepts(SN_ROUTE_TRAIN_EMBEDDED, dtype, &d)) return SN_E_UNSUPPORTED;
+  if (!holds_whole_tiles(slot_rows, n_rows, d.base)) return SN_E_BADSHAPE;
+  return launch_forward(route(TRAIN, d.base, d.bits, 0, 1, n_rows), d.base, blob, x, nullptr, n_rows, ld, 0, 1, out, acts, emb, slot_rows, 0,
+                        (hipStream_t)stream);
 }
 
+// SN_DTYPE_BF16X3 (blob: *_bwd_bf16x3 table): acts MUST be the x3 state sn_mlp_forward_train(SN_DTYPE_BF16X3) wrote (masks from its
+// sign words); g_acts leaves in the same layout ((hi, lo) pairs in slots 0..8) for sn_weight_grads(SN_DTYPE_BF16X3)
 int sn_mlp_backward_chain(const void* blob_bwd, int dtype, const float* acts, const float* out_raw, const float* g_raw,
                           long n_points, long slot_rows, float* g_acts, float* g_out, void* stream) {
   if (!blob_bwd || !acts || !out_raw || !g_raw || !g_acts || !g_out || n_points < 0) return SN_E_BADARG;
-  const bool classic = dtype & SN_DTYPE_CLASSIC_HEADS;
-  const bool compiler_scheduled = dtype & SN_DTYPE_COMPILER_SCHEDULED;
-  dtype &= ~(SN_DTYPE_CLASSIC_HEADS | SN_DTYPE_COMPILER_SCHEDULED);
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16_STATE && dtype != SN_DTYPE_BF16X3) return SN_E_UNSUPPORTED;
-  const long tile = (dtype == SN_DTYPE_F32 || dtype == SN_DTYPE_BF16X3) ? 128 : 256;      // whole point tiles are written
-  if (slot_rows < (n_points + tile - 1) / tile * tile) return SN_E_BADSHAPE;
-  // fp32-level accuracy on the bf16 MFMA (blob: *_bwd_bf16x3 table).  acts MUST be the x3 state sn_mlp_forward_train(SN_DTYPE_BF16X3)
-  // wrote (masks from its sign words); g_acts leaves in the same layout ((hi, lo) pairs in slots 0..8) for sn_weight_grads(SN_DTYPE_BF16X3)
-  if (dtype == SN_DTYPE_BF16X3) {
-    if (slot_rows % 128 != 0) return SN_E_BADSHAPE;
-    if (!compiler_scheduled && n_points < (1l << 31) - 256)  // the generated slab loop (sn_mlp_bwd_bf16x3_t.hip): the same bits
-      return SN_HEADS(classic, sn_mlp_backward_chain_bf16x3_t)(blob_bwd, acts, out_raw, g_raw, n_points, slot_rows, g_acts, g_out, (hipStream_t)stream);
-    return SN_HEADS(classic, sn_mlp_backward_chain_bf16x3)(blob_bwd, acts, out_raw, g_raw, n_points, slot_rows, g_acts, g_out, (hipStream_t)stream);
+  Dtype d;
+  if (!accepts(SN_ROUTE_CHAIN, dtype, &d)) return SN_E_UNSUPPORTED;
+  if (!holds_whole_tiles(slot_rows, n_points, d.base)) return SN_E_BADSHAPE;    // whole point tiles are written
+  if (d.base == SN_DTYPE_BF16X3 && slot_rows % 128 != 0) return SN_E_BADSHAPE;
+  const Route r = route(CHAIN, d.base, d.bits, 0, 0, n_points);
+#define SN_CHAIN(name) return SN_HEADS(r.classic, name)(blob_bwd, acts, out_raw, g_raw, n_points, slot_rows, g_acts, g_out
+  switch (r.k) {
+    case K_sn_mlp_backward_chain_f32: SN_CHAIN(sn_mlp_backward_chain_f32), (hipStream_t)stream);
+    case K_sn_mlp_backward_chain_f32g: SN_CHAIN(sn_mlp_backward_chain_f32g), (hipStream_t)stream);
+    case K_sn_mlp_backward_chain_bf16: SN_CHAIN(sn_mlp_backward_chain_bf16), d.base == SN_DTYPE_BF16_STATE, (hipStream_t)stream);
+    case K_sn_mlp_backward_chain_bf16_t: SN_CHAIN(sn_mlp_backward_chain_bf16_t), (hipStream_t)stream);
+    case K_sn_mlp_backward_chain_bf16x3: SN_CHAIN(sn_mlp_backward_chain_bf16x3), (hipStream_t)stream);
+    case K_sn_mlp_backward_chain_bf16x3_t: SN_CHAIN(sn_mlp_backward_chain_bf16x3_t), (hipStream_t)stream);
+    default: return SN_E_UNSUPPORTED;
   }
-  if (dtype == SN_DTYPE_BF16_STATE && !compiler_scheduled && n_points < (1l << 31) - 256)         // the hand-scheduled kernel
-    return SN_HEADS(classic, sn_mlp_backward_chain_bf16_t)(blob_bwd, acts, out_raw, g_raw, n_points, slot_rows, g_acts, g_out, (hipStream_t)stream);
-  if (dtype != SN_DTYPE_F32)
-    return SN_HEADS(classic, sn_mlp_backward_chain_bf16)(blob_bwd, acts, out_raw, g_raw, n_points, slot_rows, g_acts, g_out,
-                                                         dtype == SN_DTYPE_BF16_STATE, (hipStream_t)stream);
-  if (!compiler_scheduled)                       // round 6: the fragments-from-L2 chain (csrc/sn_mlp_bwd_f32g.hip): the same bits
-    return SN_HEADS(classic, sn_mlp_backward_chain_f32g)(blob_bwd, acts, out_raw, g_raw, n_points, slot_rows, g_acts, g_out, (hipStream_t)stream);
-  return SN_HEADS(classic, sn_mlp_backward_chain_f32)(blob_bwd, acts, out_raw, g_raw, n_points, slot_rows, g_acts, g_out,
-                                                      (hipStream_t)stream);
+#undef SN_CHAIN
 }
 
 int sn_generate_rays(const float* c2w, int H, int W, float focal, float near, float far, int x0, int y0, int stride_x,
@@ -380,34 +358,28 @@ int sn_dw_gemm(const void* tasks, int n_tasks, void* stream) {
 
 long sn_weight_grads_workspace_bytes(long slot_rows, int dtype) {
   if (slot_rows < 16 || slot_rows % 16 != 0) return SN_E_BADSHAPE;
-  const int emb16 = (dtype & SN_DTYPE_EMB_BF16) ? 1 : 0;
-  dtype &= ~SN_DTYPE_EMB_BF16;
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16_STATE && dtype != SN_DTYPE_BF16X3) return SN_E_UNSUPPORTED;
-  if (emb16 && dtype != SN_DTYPE_BF16_STATE) return SN_E_UNSUPPORTED;
-  return sn_weight_grads_workspace_bytes_impl(slot_rows, dtype, emb16);
+  Dtype d;
+  if (const int refused = parse_dw_dtype(dtype, &d)) return refused;
+  return sn_weight_grads_workspace_bytes_impl(slot_rows, d.base, d.bits);
 }
 
 int sn_weight_grads_plan(long slot_rows, int dtype, int32_t* out_host, int max_probs) {
   // the checks of sn_weight_grads_workspace_bytes, in its order
   if (slot_rows < 16 || slot_rows % 16 != 0) return SN_E_BADSHAPE;
-  const int emb16 = (dtype & SN_DTYPE_EMB_BF16) ? 1 : 0;
-  dtype &= ~SN_DTYPE_EMB_BF16;
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16_STATE && dtype != SN_DTYPE_BF16X3) return SN_E_UNSUPPORTED;
-  if (emb16 && dtype != SN_DTYPE_BF16_STATE) return SN_E_UNSUPPORTED;
+  Dtype d;
+  if (const int refused = parse_dw_dtype(dtype, &d)) return refused;
   if (max_probs < 0 || (max_probs > 0 && !out_host)) return SN_E_BADARG;
   static_assert(sizeof(int32_t) == sizeof(int), "plan records are int32");
-  return sn_weight_grads_plan_impl(slot_rows, dtype, emb16, reinterpret_cast<int*>(out_host), max_probs);
+  return sn_weight_grads_plan_impl(slot_rows, d.base, d.bits, reinterpret_cast<int*>(out_host), max_probs);
 }
 
 int sn_weight_grads(const void* acts, const float* emb, const void* g_acts, long slot_rows, int dtype, void* workspace,
                     float* const* grads, int accumulate, void* stream) {
   if (!acts || !emb || !g_acts || !workspace || !grads) return SN_E_BADARG;
   if (slot_rows < 16 || slot_rows % 16 != 0) return SN_E_BADSHAPE;
-  const int emb16 = (dtype & SN_DTYPE_EMB_BF16) ? 1 : 0;
-  dtype &= ~SN_DTYPE_EMB_BF16;
-  if (dtype != SN_DTYPE_F32 && dtype != SN_DTYPE_BF16 && dtype != SN_DTYPE_BF16_STATE && dtype != SN_DTYPE_BF16X3) return SN_E_UNSUPPORTED;
-  if (emb16 && dtype != SN_DTYPE_BF16_STATE) return SN_E_UNSUPPORTED;
-  return sn_weight_grads_launch(acts, emb, g_acts, slot_rows, dtype, emb16, workspace, grads, accumulate ? 1 : 0, (hipStream_t)stream);
+  Dtype d;
+  if (const int refused = parse_dw_dtype(dtype, &d)) return refused;
+  return sn_weight_grads_launch(acts, emb, g_acts, slot_rows, d.base, d.bits, workspace, grads, accumulate ? 1 : 0, (hipStream_t)stream);
 }
 
 int sn_composite_backward(const float* raw, const float* z_vals, const float* rays, const float* noise, float noise_std,
@@ -438,11 +410,9 @@ int sn_ray_grads(const float* w1, const float* w5, const float* wdir, int dtype,
   if (n_samples < 1 || n_samples > 1024) return SN_E_BADSHAPE;
   if (slot_rows < n_rays * (long)n_samples) return SN_E_BADSHAPE;
   // the layout sn_mlp_backward_chain(dtype) left g_acts in; no flag bits: the heads and the kernel generation do not change it
-  int layout;
-  if (dtype == SN_DTYPE_F32 || dtype == SN_DTYPE_BF16) layout = 0;
-  else if (dtype == SN_DTYPE_BF16_STATE) layout = 1;
-  else if (dtype == SN_DTYPE_BF16X3) layout = 2;
-  else return SN_E_UNSUPPORTED;
+  Dtype d;
+  if (!parse_dtype(dtype, 0, TRAINABLE, &d)) return SN_E_UNSUPPORTED;
+  const int layout = d.base == SN_DTYPE_BF16_STATE ? 1 : d.base == SN_DTYPE_BF16X3 ? 2 : 0;      // fp32 rows / bf16 rows / x3 state
   return sn_ray_grads_launch(w1, w5, wdir, layout, g_acts, slot_rows, rays, z_vals, n_rays, n_samples, workspace, g_rays,
                              (hipStream_t)stream);
 }
@@ -457,26 +427,6 @@ int sn_generate_rays_backward(const float* g_rays, int H, int W, float focal, in
     return SN_E_BADSHAPE;
   return sn_generate_rays_backward_launch(g_rays, H, W, focal, x0, y0, stride_x, stride_y, patch_w, patch_h, workspace, g_c2w,
                                           (hipStream_t)stream);
-}
-
-int sn_mlp_forward_embedded(const void* blob, int dtype, const float* x, long n_rows, int ld, int sigma_only,
-                            int flags, float* out, void* stream) {
-  if (!blob || !x || !out || n_rows < 0) return SN_E_BADARG;
-  if (ld < (sigma_only ? 63 : 90)) return SN_E_BADSHAPE;
-  const bool classic = (dtype & SN_DTYPE_CLASSIC_HEADS) && !sigma_only;
-  dtype &= ~SN_DTYPE_CLASSIC_HEADS;
-  if (dtype == SN_DTYPE_BF16X3)
-    return SN_HEADS(classic, sn_mlp_forward_bf16x3)(blob, x, nullptr, n_rows, ld, sigma_only, 1, out, nullptr, nullptr, 0, (hipStream_t)stream);
-  if (dtype == SN_DTYPE_F16)
-    return (classic ? sn_mlp_forward_bf16_f16_classic_launch : sn_mlp_forward_bf16_f16_launch)(
-        blob, x, nullptr, n_rows, ld, sigma_only, 1, out, nullptr, nullptr, 0, 0, (hipStream_t)stream);
-  if (dtype == SN_DTYPE_BF16)
-    return SN_HEADS(classic, sn_mlp_forward_bf16)(blob, x, nullptr, n_rows, ld, sigma_only, 1, out, nullptr, nullptr, 0, 0, (hipStream_t)stream);
-  if (dtype != SN_DTYPE_F32) return SN_E_UNSUPPORTED;
-  if (!(flags & SN_FLAG_F32_LDS_RING))
-    return SN_HEADS(classic, sn_mlp_forward_f32g)(blob, x, nullptr, n_rows, ld, sigma_only, 1, out, nullptr, nullptr, 0, (hipStream_t)stream);
-  return SN_HEADS(classic, sn_mlp_forward_f32)(blob, x, nullptr, n_rows, ld, sigma_only, 1,
-                                               out, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 int sn_composite_forward(const float* raw, int has_rgb, const float* z_vals, const float* rays, const float* noise,

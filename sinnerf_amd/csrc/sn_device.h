@@ -41,6 +41,10 @@ constexpr bool SN_NEWACT = false;
 #endif
 constexpr bool SN_NEWACT = true;
 #endif
+// one declaration for every pass of a launcher (sn_launch.h): PARAMS_ is the parenthesised parameter list
+#define SN_DECLARE_HEADS(base, PARAMS_) int base##_launch PARAMS_; int base##_classic_launch PARAMS_
+#define SN_DECLARE_HEADS_F16(base, PARAMS_)                                                                                         \
+  SN_DECLARE_HEADS(base, PARAMS_); int base##_f16_launch PARAMS_; int base##_f16_classic_launch PARAMS_
 
 // ---------------------------------------------------------------------------------------------
 // sin/cos of 2^b * x for power-of-two frequencies (reference: models/nerf.py:36-41, torch.sin(freq*x)).

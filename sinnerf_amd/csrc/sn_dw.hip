@@ -749,22 +749,8 @@ static void build_plan(HostPlan& hp, const char* acts, const char* emb, const ch
 
 }  // namespace snd
 
-extern "C" int sn_dw_f32_asm_launch(const snd::Plan* plan_host, hipStream_t stream);      // sn_dw_f32.hip
-extern "C" int sn_dw_bf16_asm_launch(const snd::Plan* plan_host, hipStream_t stream);     // sn_dw_bf16.hip
-extern "C" int sn_dw_narrow_bf16_asm_launch(const snd::Plan* plan_host, hipStream_t stream);   // sn_dw_narrow_bf16.hip
-#ifndef SN_DW_NARROW_ASM
-#define SN_DW_NARROW_ASM 1      // bf16-state narrow problems on the generated instruction streams (0: comparison build)
-#endif
-// SINNERF_DW_NARROW_COMPILER=1 in the environment keeps the compiler-scheduled narrow kernel (A/B runs; read once)
-static bool narrow_compiler_scheduled() {
-  static const bool v = [] { const char* e = getenv("SINNERF_DW_NARROW_COMPILER"); return e != nullptr && e[0] == '1'; }();
-  return v;
-}
-
 extern "C" long sn_weight_grads_workspace_bytes_impl(long slot_rows, int dtype, int emb16) {
-  // the same refusal as the launch below: a caller that asks here first (sinnerf_amd/autograd.py does) never stores a bf16 emb
-  // that the backward cannot read
-  if (emb16 && (dtype != 2 || !SN_DW_NARROW_ASM || narrow_compiler_scheduled())) return -4;
+  if (snh::emb16_refused(dtype, emb16)) return SN_E_UNSUPPORTED;      // the same refusal as the launch below (sn_launch.h)
   snd::HostPlan hp;
   snd::build_plan(hp, nullptr, nullptr, nullptr, slot_rows, dtype, emb16 != 0);
   return hp.bytes;
@@ -773,14 +759,14 @@ extern "C" long sn_weight_grads_workspace_bytes_impl(long slot_rows, int dtype, 
 // host-only introspection (sn_weight_grads_plan): the plan sn_weight_grads_launch hands to its kernels for this (slot_rows, dtype),
 // SN_DW_PLAN_FIELDS int32 per problem in build_plan's order.  No device call, no allocation.
 extern "C" int sn_weight_grads_plan_impl(long slot_rows, int dtype, int emb16, int* out, int max_probs) {
-  if (emb16 && (dtype != 2 || !SN_DW_NARROW_ASM || narrow_compiler_scheduled())) return -4;
+  if (snh::emb16_refused(dtype, emb16)) return SN_E_UNSUPPORTED;
   snd::HostPlan hp;
   snd::build_plan(hp, nullptr, nullptr, nullptr, slot_rows, dtype, emb16 != 0);
   constexpr int SN_DW_PLAN_FIELDS = 9;
   for (int i = 0; i < hp.plan.n_probs && i < max_probs; ++i) {
     const snd::Prob& q = hp.plan.p[i];
     // every partial buffer is a whole number of 256-byte lines (m * n * 4 and, for the problems that are followed by another, m * 4)
-    if (hp.c_off[i] % 256 != 0 || (hp.b_off[i] >= 0 && hp.b_off[i] % 256 != 0)) return -2;
+    if (hp.c_off[i] % 256 != 0 || (hp.b_off[i] >= 0 && hp.b_off[i] % 256 != 0)) return SN_E_TOOLARGE;
     int* r = out + i * SN_DW_PLAN_FIELDS;
     r[0] = q.variant; r[1] = q.m; r[2] = q.ldc; r[3] = q.ns; r[4] = q.per;
     r[5] = hp.group[i]; r[6] = hp.first_in_group[i];
@@ -792,7 +778,7 @@ extern "C" int sn_weight_grads_plan_impl(long slot_rows, int dtype, int emb16, i
 extern "C" int sn_weight_grads_launch(const void* acts, const float* emb, const void* G, long slot_rows, int dtype, int emb16,
                                       void* workspace, float* const* grads, int accumulate, hipStream_t stream) {
   using namespace snd;
-  if (emb16 && (dtype != 2 || !SN_DW_NARROW_ASM || narrow_compiler_scheduled())) return -4;     // SN_E_UNSUPPORTED: only the generated narrow kernel reads it
+  if (snh::emb16_refused(dtype, emb16)) return SN_E_UNSUPPORTED;     // only the generated narrow kernel reads it
   HostPlan hp;
   build_plan(hp, (const char*)acts, (const char*)emb, (const char*)G, slot_rows, dtype, emb16 != 0);
   char* ws = (char*)workspace;
@@ -806,7 +792,7 @@ extern "C" int sn_weight_grads_launch(const void* acts, const float* emb, const 
     const Plan pa = group_plan(hp, 0), pb = group_plan(hp, 1);
     rc = dtype == 0 ? sn_dw_f32_asm_launch(&pa, stream) : sn_dw_bf16_asm_launch(&pa, stream);
     if (rc) return rc;
-    if (dtype == 2 && SN_DW_NARROW_ASM && !narrow_compiler_scheduled()) {
+    if (dtype == 2 && SN_DW_NARROW_ASM && !snh::narrow_compiler_scheduled()) {
       rc = sn_dw_narrow_bf16_asm_launch(&pb, stream);
       if (rc) return rc;
     } else if (dtype == 2 && SN_DW_NARROW_2WG) {

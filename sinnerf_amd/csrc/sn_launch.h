@@ -2,8 +2,15 @@
 // set ONCE per (device, kernel) instead of on every launch (hipDeviceGetAttribute + hipFuncSetAttribute cost a few
 // microseconds each -- invisible next to a 170 ms frame, not next to the ~1 ms launches of a mixed-precision training step),
 // and nothing here synchronises or allocates, so every launcher stays capturable in a HIP graph.
+//
+// It also holds the ONE set of prototypes of every host function that crosses a translation unit (the *_launch / *_impl functions
+// sn_api.hip and sn_dw.hip call): the defining files include this header too, so a definition whose parameter list differs from the
+// declaration its callers see is a compile error (C linkage cannot be overloaded) instead of a link that shifts arguments.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdlib>
+#include "../../include/sinnerf_hip.h"
+#include "sn_device.h"
 
 namespace snh {
 
@@ -29,6 +36,27 @@ inline int cu_count() {
   return v;
 }
 
+// grid of a persistent kernel that walks `tiles` point tiles: one workgroup per CU, fewer when there are fewer tiles
+inline unsigned persistent_grid(long tiles) {
+  const int n_cu = cu_count();
+  return (unsigned)(tiles < n_cu ? tiles : n_cu);
+}
+
+// SN_DTYPE_EMB_BF16 (emb stored as bf16 in K-slot order) is refused unless the arithmetic is SN_DTYPE_BF16_STATE and the generated
+// narrow weight-gradient kernel -- the only reader of that form -- will run: a caller that asks sn_weight_grads_workspace_bytes first
+// (sinnerf_amd/autograd.py does) never stores a bf16 emb the backward cannot read.
+#ifndef SN_DW_NARROW_ASM
+#define SN_DW_NARROW_ASM 1      // bf16-state narrow problems on the generated instruction streams (0: comparison build)
+#endif
+// SINNERF_DW_NARROW_COMPILER=1 in the environment keeps the compiler-scheduled narrow kernel (A/B runs; read once)
+inline bool narrow_compiler_scheduled() {
+  static const bool v = [] { const char* e = getenv("SINNERF_DW_NARROW_COMPILER"); return e != nullptr && e[0] == '1'; }();
+  return v;
+}
+inline bool emb16_refused(int base_dtype, int emb16) {
+  return emb16 && (base_dtype != SN_DTYPE_BF16_STATE || !SN_DW_NARROW_ASM || narrow_compiler_scheduled());
+}
+
 }  // namespace snh
 
 // Raise the dynamic-LDS limit of kernel KFN_ to LDS_ bytes once per device.  Expands to a block with its own static
@@ -45,3 +73,77 @@ inline int cu_count() {
       if (sn_dev_ >= 0) __atomic_store_n(&sn_lds_set_[sn_dev_], (int)(LDS_), __ATOMIC_RELAXED);                     \
     }                                                                                                               \
   } while (0)
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// prototypes (see the top of the file).  SN_DECLARE_HEADS / SN_DECLARE_HEADS_F16 are defined next to SN_LAUNCH_NAME in sn_device.h.
+namespace snd { struct Plan; }                  // sn_dw_common.h
+extern "C" {
+#define SN_FWD_PARAMS_                                                                                                              \
+  const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld, int sigma_only, int input_mode, float* out,    \
+      float* acts, float* emb, long slot_rows
+#define SN_CHAIN_PARAMS_                                                                                                            \
+  const void* bblob, const float* acts, const float* out_raw, const float* g_raw, long n_points, long slot_rows, float* G, float* g_out
+#define SN_RAYS_PARAMS_ const void* blob, const float* rays, const float* z_vals, long n_points, int n_samples, float* out
+// forward: (rays, z_vals) or pre-embedded rows, inference and (acts != nullptr) training
+SN_DECLARE_HEADS(sn_mlp_forward_f32, (SN_FWD_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_forward_f32g, (SN_FWD_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_forward_f32g_store, (SN_FWD_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_forward_bf16x3, (SN_FWD_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS_F16(sn_mlp_forward_bf16, (SN_FWD_PARAMS_, int state_bf16, hipStream_t stream));
+// ... the hand-scheduled / generated kernels: (rays, z_vals) only
+SN_DECLARE_HEADS_F16(sn_mlp_forward_bf16_v3, (SN_RAYS_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_forward_bf16_t, (SN_RAYS_PARAMS_, float* acts, float* emb, long slot_rows, int emb16, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_forward_bf16x3_t, (SN_RAYS_PARAMS_, float* acts, float* emb, long slot_rows, hipStream_t stream));
+// backward chain
+SN_DECLARE_HEADS(sn_mlp_backward_chain_f32, (SN_CHAIN_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_backward_chain_f32g, (SN_CHAIN_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_backward_chain_bf16, (SN_CHAIN_PARAMS_, int state_bf16, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_backward_chain_bf16_t, (SN_CHAIN_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_backward_chain_bf16x3, (SN_CHAIN_PARAMS_, hipStream_t stream));
+SN_DECLARE_HEADS(sn_mlp_backward_chain_bf16x3_t, (SN_CHAIN_PARAMS_, hipStream_t stream));
+#undef SN_FWD_PARAMS_
+#undef SN_CHAIN_PARAMS_
+#undef SN_RAYS_PARAMS_
+// weight gradients (sn_dw.hip and the generated kernels it launches)
+int sn_dw_launch(const void* tasks, int n_tasks, hipStream_t stream);
+long sn_weight_grads_workspace_bytes_impl(long slot_rows, int dtype, int emb16);
+int sn_weight_grads_plan_impl(long slot_rows, int dtype, int emb16, int* out, int max_probs);
+int sn_weight_grads_launch(const void* acts, const float* emb, const void* G, long slot_rows, int dtype, int emb16, void* workspace,
+                           float* const* grads, int accumulate, hipStream_t stream);
+int sn_dw_f32_asm_launch(const snd::Plan* plan_host, hipStream_t stream);             // sn_dw_f32.hip
+int sn_dw_bf16_asm_launch(const snd::Plan* plan_host, hipStream_t stream);            // sn_dw_bf16.hip
+int sn_dw_narrow_bf16_asm_launch(const snd::Plan* plan_host, hipStream_t stream);     // sn_dw_narrow_bf16.hip
+// per-ray stages (sn_render.hip)
+int sn_sample_coarse_launch(const float* rays, long n_rays, int n_samples, int use_disp, float perturb,
+                            const float* perturb_rand, float* z_out, hipStream_t stream);
+int sn_composite_forward_launch(const float* raw, int has_rgb, const float* z_vals, const float* rays,
+                                const float* noise, float noise_std, long n_rays, int n_samples, int white_back,
+                                float* rgb, float* depth, float* weights, hipStream_t stream);
+int sn_composite_backward_launch(const float* raw, const float* z_vals, const float* rays, const float* noise,
+                                 float noise_std, long n_rays, int n_samples, int white_back, const float* g_rgb,
+                                 const float* g_depth, const float* g_w, float* g_raw, hipStream_t stream);
+int sn_composite_backward_rays_launch(const float* raw, const float* z_vals, const float* rays, const float* noise,
+                                      float noise_std, long n_rays, int n_samples, int white_back, const float* g_rgb,
+                                      const float* g_depth, const float* g_w, float* g_raw, float* g_rays, hipStream_t stream);
+int sn_sample_pdf_launch(const float* z_vals, const float* weights, const float* u, long n_rays, int n_samples,
+                         int n_importance, float* z_fine, float* z_merged, hipStream_t stream);
+int sn_sample_pdf_bins_launch(const float* bins, const float* weights, const float* u, long n_rays, int n_bins,
+                              int n_importance, float eps, float* samples, hipStream_t stream);
+// the steps around the hot path (sn_next.hip) and the ray gradients (sn_ray_grad.hip)
+int sn_generate_rays_launch(const float* c2w, int H, int W, float focal, float near, float far, int x0, int y0, int sx,
+                            int sy, int pw, int ph, float* rays, hipStream_t stream);
+long sn_generate_rays_backward_workspace_bytes_impl();
+int sn_generate_rays_backward_launch(const float* g_rays, int H, int W, float focal, int x0, int y0, int sx, int sy, int pw,
+                                     int ph, void* workspace, float* g_c2w, hipStream_t stream);
+int sn_adam_step_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
+                        float wd, int step, hipStream_t stream);
+long sn_render_loss_workspace_bytes_impl();
+int sn_render_loss_launch(const float* rgb_c, const float* rgb_f, const float* depth_c, const float* depth_f,
+                          const float* rgb_gt, const float* depth_gt, const unsigned char* mask, int mask_mode, long n,
+                          float w_rgb, float w_depth, float* g_rgb_c, float* g_rgb_f, float* g_depth_c, float* g_depth_f,
+                          void* workspace, float* out, hipStream_t stream);
+long sn_ray_grads_workspace_bytes_impl(long n_rays, int n_samples);
+int sn_ray_grads_launch(const float* w1, const float* w5, const float* wdir, int layout, const void* g_acts, long slot_rows,
+                        const float* rays, const float* z_vals, long n_rays, int n_samples, void* workspace, float* g_rays,
+                        hipStream_t stream);
+}  // extern "C"

@@ -439,13 +439,12 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_backward_chain_bf16)(const void* bblob, con
   using namespace snk;
   if (n_points <= 0) return 0;
   const long tiles = (n_points + 255) / 256;
-  if (slot_rows < tiles * 256) return -1;
-  const int n_cu = snh::cu_count();
+  if (slot_rows < tiles * 256) return SN_E_BADARG;
 #define SN_LAUNCH(S16_)                                                                                            \
   do {                                                                                                             \
     auto kfn = mlp_bwd_chain_bf16_kernel<S16_>;                                                                    \
     SN_ENSURE_DYN_LDS(kfn, BWD16_LDS_BYTES);                                                                       \
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(tiles < n_cu ? tiles : n_cu)), dim3(256), BWD16_LDS_BYTES, stream,     \
+    hipLaunchKernelGGL(kfn, dim3(snh::persistent_grid(tiles)), dim3(256), BWD16_LDS_BYTES, stream,                 \
                        reinterpret_cast<const char*>(bblob), acts, out_raw, g_raw, n_points, slot_rows, G, g_out); \
   } while (0)
   if (state_bf16) SN_LAUNCH(true); else SN_LAUNCH(false);

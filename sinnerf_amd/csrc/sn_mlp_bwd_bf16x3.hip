@@ -316,10 +316,9 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_backward_chain_bf16x3)(const void* bblob, c
   using namespace snk;
   if (n_points <= 0) return 0;
   const long tiles = (n_points + 127) / 128;
-  if (slot_rows < tiles * 128) return -1;
-  const int n_cu = snh::cu_count();
+  if (slot_rows < tiles * 128) return SN_E_BADARG;
   SN_ENSURE_DYN_LDS(mlp_bwd_chain_bf16x3_kernel, BX3_LDS_BYTES);
-  hipLaunchKernelGGL(mlp_bwd_chain_bf16x3_kernel, dim3((unsigned)(tiles < n_cu ? tiles : n_cu)), dim3(256), BX3_LDS_BYTES, stream,
+  hipLaunchKernelGGL(mlp_bwd_chain_bf16x3_kernel, dim3(snh::persistent_grid(tiles)), dim3(256), BX3_LDS_BYTES, stream,
                      reinterpret_cast<const char*>(bblob), acts, out_raw, g_raw, n_points, slot_rows, G, g_out);
   return (int)hipGetLastError();
 }

@@ -259,13 +259,12 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_backward_chain_f32g)(const void* bblob, con
                                                           float* g_out, hipStream_t stream) {
   using namespace snk;
   if (n_points <= 0) return 0;
-  if (slot_rows < (n_points + 127) / 128 * 128) return -1;      // whole 128-point tiles of G are written
+  if (slot_rows < (n_points + 127) / 128 * 128) return SN_E_BADARG;      // whole 128-point tiles of G are written
   const long tiles = (n_points + 127) / 128;
-  if (tiles > 0x7fffffffL) return -2;
-  const int n_cu = snh::cu_count();              // persistent: one workgroup per CU (~430 registers per lane: one wave per SIMD)
-  auto kfn = mlp_bwd_chain_f32g_kernel;
+  if (tiles > 0x7fffffffL) return SN_E_TOOLARGE;
+  auto kfn = mlp_bwd_chain_f32g_kernel;            // persistent: one workgroup per CU (~430 registers per lane: one wave per SIMD)
   SN_ENSURE_DYN_LDS(kfn, BWDG_LDS_BYTES);
-  hipLaunchKernelGGL(kfn, dim3((unsigned)(tiles < n_cu ? tiles : n_cu)), dim3(256), BWDG_LDS_BYTES, stream,
+  hipLaunchKernelGGL(kfn, dim3(snh::persistent_grid(tiles)), dim3(256), BWDG_LDS_BYTES, stream,
                      reinterpret_cast<const char*>(bblob), acts, out_raw, g_raw, n_points, slot_rows, G, g_out);
   return (int)hipGetLastError();
 }

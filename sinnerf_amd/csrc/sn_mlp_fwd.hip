@@ -324,10 +324,9 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_forward_f32)(const void* blob, const float*
   if (n_points <= 0) return 0;
   const long tiles = (n_points + 127) / 128;
   const bool store = acts != nullptr;
-  if (store && (sigma_only || emb == nullptr || slot_rows < tiles * 128)) return -1;
+  if (store && (sigma_only || emb == nullptr || slot_rows < tiles * 128)) return SN_E_BADARG;
   // persistent launch: one workgroup per CU (the 135 KB LDS ring admits exactly one), each walks tiles b, b+grid, ...
-  const int n_cu = snh::cu_count();
-  dim3 grid((unsigned)(tiles < n_cu ? tiles : n_cu)), block(256);
+  dim3 grid(snh::persistent_grid(tiles)), block(256);
   const size_t lds = MLP_F32_LDS_BYTES_V2 + (store ? XPOSE_LDS_BYTES : EPI_LDS_BYTES);
   const char* b = reinterpret_cast<const char*>(blob);
 #define SN_LAUNCH(SO, IM, ST)                                                                                    \
@@ -340,7 +339,7 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_forward_f32)(const void* blob, const float*
     if (input_mode == 0) SN_LAUNCH(false, 0, true); else SN_LAUNCH(false, 1, true);
 #ifdef SN_CLASSIC_HEADS                         // the sigma-only kernels never reach the heads: sn_api.hip routes them to the main pass
   } else if (sigma_only) {
-    return -4;
+    return SN_E_UNSUPPORTED;
   } else if (input_mode == 0) {
     SN_LAUNCH(false, 0, false);
   } else {

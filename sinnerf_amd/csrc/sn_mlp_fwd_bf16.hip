@@ -440,9 +440,8 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_forward_bf16)(const void* blob, const float
   if (n_points <= 0) return 0;
   const long tiles = (n_points + 255) / 256;
   const bool store = acts != nullptr;
-  if (store && (sigma_only || emb == nullptr || slot_rows < tiles * 256)) return -1;
-  const int n_cu = snh::cu_count();
-  dim3 grid((unsigned)(tiles < n_cu ? tiles : n_cu)), block(256);
+  if (store && (sigma_only || emb == nullptr || slot_rows < tiles * 256)) return SN_E_BADARG;
+  dim3 grid(snh::persistent_grid(tiles)), block(256);
   const size_t lds = MLP_BF16_LDS_BYTES + (store ? BF16_XPOSE_LDS_BYTES : 0);
   const char* b = reinterpret_cast<const char*>(blob);
 #define SN_LAUNCH(SO, IM, ST)                                                                                    \
@@ -453,10 +452,10 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_forward_bf16)(const void* blob, const float
   } while (0)
   if (store) {
     if (input_mode == 0) { if (state_bf16) SN_LAUNCH(false, 0, 2); else SN_LAUNCH(false, 0, 1); }
-    else { if (state_bf16) SN_LAUNCH(false, 1, 2); else return -4; }    // embedded rows + fp32 state: out of registers, not built
+    else { if (state_bf16) SN_LAUNCH(false, 1, 2); else return SN_E_UNSUPPORTED; }    // embedded rows + fp32 state: out of registers, not built
   }
 #ifdef SN_CLASSIC_HEADS                         // the sigma-only kernels never reach the heads: sn_api.hip routes them to the main pass
-  else if (sigma_only) return -4;
+  else if (sigma_only) return SN_E_UNSUPPORTED;
   else if (input_mode == 0) SN_LAUNCH(false, 0, 0);
   else SN_LAUNCH(false, 1, 0);
 #else

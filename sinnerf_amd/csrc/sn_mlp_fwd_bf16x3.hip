@@ -380,9 +380,8 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_forward_bf16x3)(const void* blob, const flo
   if (n_points <= 0) return 0;
   const long tiles = (n_points + 127) / 128;
   const bool store = acts != nullptr;
-  if (store && (sigma_only || emb == nullptr || slot_rows < tiles * 128)) return -1;
-  const int n_cu = snh::cu_count();
-  dim3 grid((unsigned)(tiles < n_cu ? tiles : n_cu)), block(256);
+  if (store && (sigma_only || emb == nullptr || slot_rows < tiles * 128)) return SN_E_BADARG;
+  dim3 grid(snh::persistent_grid(tiles)), block(256);
   const char* b = reinterpret_cast<const char*>(blob);
   const size_t lds = X3_LDS_BYTES + (store ? XPOSE_LDS_BYTES : 0);
 #define SN_LAUNCH(SO, IM, ST)                                                                                        \
@@ -393,7 +392,7 @@ extern "C" int SN_LAUNCH_NAME(sn_mlp_forward_bf16x3)(const void* blob, const flo
   } while (0)
   if (store) { if (input_mode == 0) SN_LAUNCH(false, 0, true); else SN_LAUNCH(false, 1, true); }
 #ifdef SN_CLASSIC_HEADS                         // the sigma-only kernels never reach the heads: sn_api.hip routes them to the main pass
-  else if (sigma_only) return -4;
+  else if (sigma_only) return SN_E_UNSUPPORTED;
   else if (input_mode == 0) SN_LAUNCH(false, 0, false);
   else SN_LAUNCH(false, 1, false);
 #else

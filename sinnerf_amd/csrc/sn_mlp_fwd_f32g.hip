@@ -20,7 +20,9 @@
 //         in its groups 4 t ..), so no layer end drains the matrix pipe.
 //   * what VALU work is left sits where it cannot be avoided: the embeddings (exact range reduction), the sigma head's 256 FMAs,
 //     ShiftedSoftplus and the rgb head -- 2.6 k instructions per 128-point tile beside 9 280 MFMAs per wave.
-// The training forward (activation stores) and the backward chain stay on sn_mlp_fwd.hip / sn_mlp_bwd.hip (LDS ring, same epilogues).
+// The training forward (activation stores) is this kernel's STORE instantiation, compiled as a translation unit of its own (see the
+// launcher below); the backward chain of the same generation is sn_mlp_bwd_f32g.hip.  sn_mlp_fwd.hip / sn_mlp_bwd.hip (LDS ring, same
+// epilogues, same bits) remain behind SN_FLAG_F32_LDS_RING / SN_DTYPE_COMPILER_SCHEDULED.
 #include "sn_mlp_f32g.h"
 
 namespace snk {
@@ -369,9 +371,8 @@ extern "C" int SN_F32G_LAUNCH_NAME(SN_F32G_ENTRY)(const void* blob, const float*
   if (n_points <= 0) return 0;
   const long tiles = (n_points + 127) / 128;
   const bool store = acts != nullptr;
-  if (store && (sigma_only || emb == nullptr || slot_rows < tiles * 128)) return -1;
-  const int n_cu = snh::cu_count();              // persistent: one workgroup per CU (~400 registers per lane: one wave per SIMD)
-  dim3 grid((unsigned)(tiles < n_cu ? tiles : n_cu)), block(256);
+  if (store && (sigma_only || emb == nullptr || slot_rows < tiles * 128)) return SN_E_BADARG;
+  dim3 grid(snh::persistent_grid(tiles)), block(256);      // persistent: one workgroup per CU (~400 registers per lane: one wave per SIMD)
   const size_t lds = store ? F32G_LDS_BYTES_STORE : F32G_LDS_BYTES;
   const char* b = reinterpret_cast<const char*>(blob);
 #define SN_LAUNCH(SO, IM, ST)                                                                                       \
@@ -382,20 +383,20 @@ extern "C" int SN_F32G_LAUNCH_NAME(SN_F32G_ENTRY)(const void* blob, const float*
   } while (0)
 #if defined(SN_F32G_AB)                         // timing builds (tools/build_variant_f32g.sh): ONE instantiation: the frame render's, or
 #ifdef SN_F32G_AB_STORE                         // the training forward's with -DSN_F32G_AB_STORE (which replaces BOTH objects)
-  if (!store || input_mode != 0) return -4;
+  if (!store || input_mode != 0) return SN_E_UNSUPPORTED;
   SN_LAUNCH(false, 0, true);
 #else
-  if (store || sigma_only || input_mode != 0) return -4;
+  if (store || sigma_only || input_mode != 0) return SN_E_UNSUPPORTED;
   SN_LAUNCH(false, 0, false);
 #endif
 #elif defined(SN_F32G_TU_STORE)
-  if (!store) return -4;
+  if (!store) return SN_E_UNSUPPORTED;
   if (input_mode == 0) SN_LAUNCH(false, 0, true); else SN_LAUNCH(false, 1, true);
 #elif defined(SN_CLASSIC_HEADS)                 // the sigma-only kernels never reach the heads: sn_api.hip routes them to the main pass
-  if (store || sigma_only) return -4;
+  if (store || sigma_only) return SN_E_UNSUPPORTED;
   if (input_mode == 0) SN_LAUNCH(false, 0, false); else SN_LAUNCH(false, 1, false);
 #else
-  if (store) return -4;
+  if (store) return SN_E_UNSUPPORTED;
   if (input_mode == 0) { if (sigma_only) SN_LAUNCH(true, 0, false); else SN_LAUNCH(false, 0, false); }
   else { if (sigma_only) SN_LAUNCH(true, 1, false); else SN_LAUNCH(false, 1, false); }
 #endif

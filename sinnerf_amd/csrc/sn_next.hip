@@ -13,6 +13,7 @@
 //                          -- two small launches instead of ~20 elementwise/reduction launches and their HBM round trips.
 // All are HBM-bound elementwise kernels: coalesced, 16-byte accesses where the layout allows.
 #include "sn_device.h"
+#include "sn_launch.h"
 
 namespace snx {
 

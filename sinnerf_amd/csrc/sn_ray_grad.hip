@@ -267,10 +267,9 @@ extern "C" int sn_ray_grads_launch(const float* w1, const float* w5, const float
   if (n_rays <= 0) return 0;
   const long n_points = n_rays * (long)n_samples;
   const long tiles = (n_points + PTS_WG - 1) / PTS_WG;
-  const long cus = snh::cu_count();
-  const unsigned grid = (unsigned)(tiles < cus ? tiles : cus);
+  const unsigned grid = snh::persistent_grid(tiles);
   const long ray_blocks = (n_rays + 3) / 4;
-  if (ray_blocks > 0x7fffffffL) return -2;
+  if (ray_blocks > 0x7fffffffL) return SN_E_TOOLARGE;
   constexpr size_t lds = LDS_FLOATS * sizeof(float);
   float* scratch = reinterpret_cast<float*>(workspace);
   const char* G = reinterpret_cast<const char*>(g_acts);

@@ -12,6 +12,7 @@
 // torch's CPU cumsum/cumprod accumulate fp32 inputs in double and round per element; the scans here do the
 // same (fp64 scan, one rounding), which also makes the result independent of the scan tree.
 #include "sn_device.h"
+#include "sn_launch.h"
 
 namespace snr {
 
@@ -420,7 +421,7 @@ sample_pdf_kernel(const float* __restrict__ z_vals, const float* __restrict__ we
 extern "C" int sn_sample_coarse_launch(const float* rays, long n_rays, int n_samples, int use_disp, float perturb,
                                        const float* perturb_rand, float* z_out, hipStream_t stream) {
   if (n_rays <= 0) return 0;
-  if (perturb > 0.0f && perturb_rand == nullptr) return -3;
+  if (perturb > 0.0f && perturb_rand == nullptr) return SN_E_MISSING_RNG;
   const long total = n_rays * (long)n_samples;
   long blocks = (total + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
@@ -436,9 +437,9 @@ extern "C" int sn_composite_forward_launch(const float* raw, int has_rgb, const 
   using namespace snr;
   if (n_rays <= 0) return 0;
   const int C = (n_samples + 63) / 64;
-  if (C < 1 || C > 16) return -4;
+  if (C < 1 || C > 16) return SN_E_UNSUPPORTED;
   const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return -2;
+  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
   dim3 grid((unsigned)blocks), block(256);
 #define SN_CL(CC)                                                                                                \
   case CC:                                                                                                       \
@@ -460,9 +461,9 @@ extern "C" int sn_composite_backward_launch(const float* raw, const float* z_val
   using namespace snr;
   if (n_rays <= 0) return 0;
   const int C = (n_samples + 63) / 64;
-  if (C < 1 || C > 16) return -4;
+  if (C < 1 || C > 16) return SN_E_UNSUPPORTED;
   const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return -2;
+  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
   dim3 grid((unsigned)blocks), block(256);
 #define SN_CB(CC)                                                                                                \
   case CC:                                                                                                       \
@@ -483,9 +484,9 @@ extern "C" int sn_composite_backward_rays_launch(const float* raw, const float* 
   using namespace snr;
   if (n_rays <= 0) return 0;
   const int C = (n_samples + 63) / 64;
-  if (C < 1 || C > 16) return -4;
+  if (C < 1 || C > 16) return SN_E_UNSUPPORTED;
   const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return -2;
+  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
   dim3 grid((unsigned)blocks), block(256);
 #define SN_CBR(CC)                                                                                               \
   case CC:                                                                                                       \
@@ -502,11 +503,11 @@ extern "C" int sn_sample_pdf_launch(const float* z_vals, const float* weights, c
                                     int n_samples, int n_importance, float* z_fine, float* z_merged,
                                     hipStream_t stream) {
   if (n_rays <= 0) return 0;
-  if (n_samples < 3 || n_importance < 1) return -5;
+  if (n_samples < 3 || n_importance < 1) return SN_E_BADSHAPE;
   const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return -2;
+  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
   const size_t lds = 4 * (size_t)(2 * (n_samples - 1) + 2 * (n_samples + n_importance)) * sizeof(float);
-  if (lds > 64 * 1024) return -4;
+  if (lds > 64 * 1024) return SN_E_UNSUPPORTED;
   hipLaunchKernelGGL(snr::sample_pdf_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, stream, z_vals, weights, u,
                      n_rays, n_samples, n_importance, 1e-5f /* render_rays calls sample_pdf with its default eps */, z_fine, z_merged);
   return (int)hipGetLastError();
@@ -516,12 +517,12 @@ extern "C" int sn_sample_pdf_launch(const float* z_vals, const float* weights, c
 extern "C" int sn_sample_pdf_bins_launch(const float* bins, const float* weights, const float* u, long n_rays,
                                          int n_bins, int n_importance, float eps, float* samples, hipStream_t stream) {
   if (n_rays <= 0) return 0;
-  if (n_bins < 1 || n_importance < 1) return -5;
+  if (n_bins < 1 || n_importance < 1) return SN_E_BADSHAPE;
   const int S = n_bins + 2;
   const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return -2;
+  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
   const size_t lds = 4 * (size_t)(2 * (S - 1) + S + n_importance) * sizeof(float);
-  if (lds > 64 * 1024) return -4;
+  if (lds > 64 * 1024) return SN_E_UNSUPPORTED;
   hipLaunchKernelGGL(snr::sample_pdf_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, stream, bins, weights, u,
                      n_rays, S, n_importance, eps, samples, (float*)nullptr);
   return (int)hipGetLastError();

@@ -428,8 +428,8 @@ def test_empty_batch_and_unsupported_sizes():
     assert rc != 0
     with pytest.raises(SinnerfHipError):
         _lib.check(rc, "sn_composite_forward")
-    # ... while render_rays itself takes such a call (and other layer / embedding configurations) through the general torch-op
-    # path on the device: tests/test_training_kernels_system_gpu.py::test_general_configurations_*
+    # ... and so does render_rays itself for such a call (and for other layer / embedding configurations): there is no general
+    # torch-op path, tests/test_training_kernels_system_gpu.py::test_unsupported_configurations_are_refused_loudly
 
 
 def test_bf16_hand_scheduled_kernel_equals_compiler_scheduled():
