@@ -11,7 +11,8 @@ instructions relative to inline-asm MFMAs, so the whole trunk is emitted as ONE 
 
   * backbone: the MFMAs in execution order (slab, k-step, point tile); two accumulator sets alternate between slabs, the
     bias enters as the C operand of a slab's first k-step (no accumulator initialisation moves);
-  * fillers, dealt into the gaps after each MFMA by a list scheduler (release gap, deadline, per-gap issue budget):
+  * fillers, dealt into the gaps after each MFMA by a list scheduler (release gap, deadline, per-gap issue budget;
+    tools/mfma_stream.py, shared with the other generators of such statements):
       - A-fragment ds_read_b128, PREFETCH k-steps ahead through a register ring, waited for with COUNTED lgkmcnt(N);
       - bias ds_reads of the next slab;
       - the deferred epilogue of the previous slab (cvt_pk / pk_max / accvgpr_write into the other activation set),
@@ -33,7 +34,12 @@ Register plan inside the statement (physical registers, all declared as clobbers
 
 usage: gen_bf16_trunk.py out.inc [knob=value ...]     knobs: see KNOBS below (ablation builds for tools/ timing)
 """
+import os
 import sys
+from types import SimpleNamespace
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mfma_stream as S                         # noqa: E402  (Emitter, Backbone, Scheduler, Filler, write_inc)
 
 # ------------------------------------------------------------------------------------------------------------------
 KNOBS = dict(prefetch=4,        # A-fragment prefetch distance in k-steps (ring = prefetch + 2 entries)
@@ -143,216 +149,50 @@ WRITE_SET = {0: 0, 1: 1, 2: 0, 3: 1, 4: 0, 5: 1, 6: 0, 7: 1, 8: 0}
 def act_reg(st, kstep, pt): return st * 128 + (kstep * 2 + pt) * 4
 
 
-class Filler:
-    __slots__ = ("text", "cost", "release", "deadline", "kind", "reads", "writes", "tag", "seq")
-    def __init__(self, text, cost, release, deadline, kind, reads=(), writes=(), tag=None):
-        self.text, self.cost, self.release, self.deadline, self.kind = text, cost, release, deadline, kind
-        self.reads, self.writes, self.tag = set(reads), set(writes), tag
-        self.seq = 0
+def plan(K):
+    """what the builders below share for one gen() call: the knobs, the backbone, ring geometry, operand-format mnemonics"""
+    P = SimpleNamespace(K=K, D=K["prefetch"], R=K["prefetch"] + 2, store=K["store"])
+    P.bb = S.Backbone(N_SLABS_TRUNK, lambda s: slab_kind(s)[1] + slab_kind(s)[2], 2)      # mf[i] = (slab, k-step, point tile)
+    assert P.R <= 7, "fragment ring: 7 entries of registers"
+    assert not P.store or P.R <= 6, "store mode keeps v232..v235 for itself"
+    P.n_slots = ST_N_SLOTS if P.store else N_SLOTS
+    P.dma_dist = ST_DMA_DIST if P.store else DMA_DIST
+    # f16=1: the same stream with fp16 operands (same issue classes and latencies)
+    P.cvt = "v_cvt_pk_f16_f32" if K["f16"] else "v_cvt_pk_bf16_f32"
+    P.mfma = "v_mfma_f32_32x32x16_f16" if K["f16"] else "v_mfma_f32_32x32x16_bf16"
+    return P
 
 
-class Gen:
-    def __init__(self, knobs):
-        self.k = knobs
-        self.out = []                 # emitted instruction texts
-        self.lgkm = []                # outstanding LDS reads (tags) in issue order
-        self.vm = [1, 2, 3, 4]        # outstanding LDS-DMA pieces (issue-order tags) on entry: at most the single pieces of
-                                      # slabs 1..4, issued by the previous tile's dir_encoding section / the prologue
-        if knobs["store"]:
-            self.vm = [1, 2]          # ... store mode (distance 3): slabs 1, 2.  Older memory operations of the kernel that are
-                                      # still in flight only make the first counted waits stricter (vmcnt retires in order)
-        self.last_salu_write = {}     # SGPR -> wait-state clock of the SALU instruction that wrote it (SALU -> VMEM address: 5 states)
-        self.last_valu_write = {}     # reg -> index in self.out of the VALU instruction that wrote it
-        self.n_states = 0             # wait states issued so far (every instruction = 1, s_nop n = n + 1)
-        self.state_at = []            # wait-state clock of each emitted instruction
-        self.last_m0 = -10
-        self.mfma_count = 0
-        self.stats = dict(nop=0, wait=0, forced=0)
+def ring(P, kidx): return RING0 + 4 * (kidx % P.R)       # kidx = global k-step counter over the trunk
 
-    # ---- raw emission --------------------------------------------------------------------------------------------
-    def emit(self, text, writes=(), valu=False, states=1):
-        self.out.append(text)
-        self.state_at.append(self.n_states)
-        if valu:
-            for r in writes:
-                self.last_valu_write[r] = self.n_states
-        self.n_states += states
+def frag_read(P, kidx):
+    s, ks = P.bb.kstep_list[kidx]
+    slot, r = s % P.n_slots, ring(P, kidx)
+    base = ("%[va0]", "v%d" % VA1, "v%d" % VA2)[slot // SLOTS_PER_BASE]
+    return "ds_read_b128 v[%d:%d], %s offset:%d" % (r, r + 3, base, (slot % SLOTS_PER_BASE) * SLOT_BYTES + ks * 1024)
 
-    def nop(self, n):                 # n wait states
-        while n > 0:
-            c = min(n, 8)
-            self.emit("s_nop %d" % (c - 1), states=c)
-            self.stats["nop"] += 1
-            n -= c
-
-    def pad_valu_to_mfma(self, regs):
-        """VALU write -> MFMA read of the same register needs 2 wait states in between."""
-        need = 0
-        for r in regs:
-            w = self.last_valu_write.get(r)
-            if w is not None:
-                need = max(need, 3 - (self.n_states - w))      # writer at clock w; reader must be at >= w + 3
-        if need > 0:
-            self.nop(need)
-
-    def pad_valu_to_swap(self, regs):
-        """VALU write -> v_permlane32_swap_b32 read of the same register: 2 wait states (what hipcc inserts for its own code)."""
-        self.pad_valu_to_mfma(regs)
-
-    def pad_salu_to_vmem(self, sregs):
-        need = 0
-        for r in sregs:
-            w = self.last_salu_write.get(r)
-            if w is not None:
-                need = max(need, 6 - (self.n_states - w))
-        if need > 0:
-            self.nop(need)
-
-    def wait_lgkm(self, tags):
-        """counted wait: every LDS read carrying one of `tags` has returned (LDS reads return in order)."""
-        pos = -1
-        for i, t in enumerate(self.lgkm):
-            if t in tags:
-                pos = i
-        if pos < 0:
-            return
-        n = len(self.lgkm) - 1 - pos
-        assert n <= 15, "lgkmcnt field is 4 bits"
-        self.emit("s_waitcnt lgkmcnt(%d)" % n)
-        self.stats["wait"] += 1
-        del self.lgkm[:pos + 1]
-
-    def wait_vm(self, tag):
-        """counted wait on the vector-memory queue (retires in issue order): the operation carrying `tag` has completed.  The count
-        field has 6 bits: a target with more than 63 younger operations is covered by vmcnt(63) (at most the 63 youngest remain)."""
-        if tag not in self.vm:
-            return
-        pos = max(i for i, t in enumerate(self.vm) if t == tag)
-        self.emit("s_waitcnt vmcnt(%d)" % min(63, len(self.vm) - 1 - pos))
-        self.stats["wait"] += 1
-        del self.vm[:pos + 1]
-
-    def run_filler(self, f):
-        k = f.kind
-        if k == "ds_read":
-            self.emit(f.text)
-            self.lgkm.append(f.tag)
-        elif k == "vload":                               # global load into registers of the statement (waited for with wait_vm)
-            self.pad_salu_to_vmem(f.reads)
-            self.emit(f.text)
-            self.vm.append(f.tag)
-        elif k == "valu":
-            if f.tag is not None:                        # needs LDS data (sigma weights) / a loaded register (("vm", tag))
-                if f.tag[0] == "vm":
-                    self.wait_vm(f.tag[1])
-                else:
-                    self.wait_lgkm({f.tag})
-            self.emit(f.text, writes=f.writes, valu=True)
-        elif k == "ds_write":
-            self.emit(f.text)
-            self.lgkm.append(("stw",))
-        elif k == "swap":
-            self.pad_valu_to_swap(f.reads)
-            self.emit(f.text, writes=f.writes, valu=True)
-        elif k == "salu":
-            self.emit(f.text)
-            for r in f.writes:
-                self.last_salu_write[r] = self.n_states - 1
-        elif k == "vstore":
-            if f.tag is not None:                        # the staged row has arrived in its registers
-                self.wait_lgkm({f.tag})
-            self.pad_salu_to_vmem(f.reads)
-            self.emit(f.text)
-            self.vm.append(10 ** 9)                      # never the target of a counted wait: only ever counts as "younger"
-        elif k == "m0":
-            self.emit(f.text)
-            self.last_m0 = self.n_states - 1
-        elif k == "dma":
-            if self.n_states - self.last_m0 < 2:         # s_mov m0 -> LDS-DMA: one wait state
-                self.nop(1)
-            self.dma_seen = getattr(self, "dma_seen", 0) + 1
-            if self.dma_seen % self.k["dma_thin"] == 0:
-                if self.k["dma_exec"]:
-                    self.emit("s_mov_b64 exec, %[em]")
-                self.emit(f.text)
-                if self.k["dma_exec"]:
-                    self.emit("s_mov_b64 exec, -1")
-                self.vm.append(f.tag)
-        elif k == "bar":
-            # own pieces of the NEXT slab have landed (later slabs may still be in flight: counted vmcnt), then all waves meet
-            nxt = f.tag
-            pos = -1
-            for i, t in enumerate(self.vm):
-                if isinstance(t, int) and t <= nxt:
-                    pos = i
-            if pos >= 0:
-                self.emit("s_waitcnt vmcnt(%d)" % min(63, len(self.vm) - 1 - pos))   # (6-bit field: a larger count only waits for more)
-                del self.vm[:pos + 1]
-            self.emit("s_barrier")
-        else:
-            self.emit(f.text)
+def bias_read(s, q):
+    return "ds_read_b128 v[%d:%d], %%[vb] offset:%d" % (BIAS + 4 * q, BIAS + 4 * q + 3, s * 128 + q * 16)
 
 
-def gen(knobs):
-    g = Gen(knobs)
-    K = knobs
-    D = K["prefetch"]
-    R = D + 2
-    ring = lambda kidx: RING0 + 4 * (kidx % R)           # kidx = global k-step counter over the trunk
+def add_fragments(P, sched):
+    """A fragments.  The first D k-steps of the trunk are loaded in the preamble (slab 0 is resident: the previous tile's / the
+    prologue's barrier guaranteed it)"""
+    K, D, R, first, idx_of, ksl = P.K, P.D, P.R, P.bb.first, P.bb.idx_of, P.bb.kstep_list
+    for kidx in range(D, len(ksl) if K["frag"] else 0):
+        s, ks = ksl[kidx]
+        # release: after the previous user of this ring entry has issued (k-step kidx - R, its pt-1 MFMA) and, when the
+        # fragment belongs to a LATER slab than the one executing at that point, after that slab's barrier
+        prev_user = idx_of[ksl[kidx - R] + (1,)] if kidx - R >= 0 else -1
+        rel = max(prev_user, idx_of[ksl[kidx - D] + (0,)])                                # ideal gap: D k-steps ahead
+        bar_ok = first[s - 1] + K["bar_gap"] if s > 0 else -1                            # barrier(s-1) makes slab s visible
+        rel = max(rel, bar_ok + 1) if K["bar"] else rel
+        sched.add(S.Filler(frag_read(P, kidx), K["lds_cost"], rel, idx_of[(s, ks, 0)] - 1, "ds_read", tag=("frag", kidx)))
 
-    # ---- backbone -------------------------------------------------------------------------------------------------
-    # mf[i] = (slab, ks, pt); gk[(slab, ks)] = global k-step index; first[(slab)] = index of its first MFMA
-    mf, gk, first, nk = [], {}, {}, {}
-    kc = 0
-    for s in range(N_SLABS_TRUNK):
-        _, nx, na = slab_kind(s)
-        nk[s] = nx + na
-        first[s] = len(mf)
-        for ks in range(nk[s]):
-            gk[(s, ks)] = kc
-            kc += 1
-            for pt in range(2):
-                mf.append((s, ks, pt))
-    first[N_SLABS_TRUNK] = len(mf)
-    total_k = kc
-    kstep_list = [(s, ks) for s in range(N_SLABS_TRUNK) for ks in range(nk[s])]
-    idx_of = {m: i for i, m in enumerate(mf)}
 
-    fillers = []
-    seq = [0]
-    def add(f):
-        f.seq = seq[0]; seq[0] += 1
-        fillers.append(f)
-
-    assert R <= 7, "fragment ring: 7 entries of registers"
-    STORE = K["store"]
-    n_slots = ST_N_SLOTS if STORE else N_SLOTS
-    dma_dist = ST_DMA_DIST if STORE else DMA_DIST
-    assert not STORE or R <= 6, "store mode keeps v232..v235 for itself"
-    def frag_addr(s, ks):
-        slot = s % n_slots
-        return ("%[va0]", "v%d" % VA1, "v%d" % VA2)[slot // SLOTS_PER_BASE], (slot % SLOTS_PER_BASE) * SLOT_BYTES + ks * 1024
-
-    # ---- A fragments ------------------------------------------------------------------------------------------------
-    # the first D k-steps of the trunk are loaded in the preamble (slab 0 is resident: the previous tile's / the prologue's
-    # barrier guaranteed it)
-    if K["frag"]:
-        for kidx, (s, ks) in enumerate(kstep_list):
-            use = idx_of[(s, ks, 0)]
-            if kidx < D:
-                continue
-            # release: after the previous user of this ring entry has issued (k-step kidx - R, its pt-1 MFMA) and, when the
-            # fragment belongs to a LATER slab than the one executing at that point, after that slab's barrier
-            prev_user = idx_of[(kstep_list[kidx - R][0], kstep_list[kidx - R][1], 1)] if kidx - R >= 0 else -1
-            want = idx_of[(kstep_list[kidx - D][0], kstep_list[kidx - D][1], 0)]      # ideal gap: D k-steps ahead
-            rel = max(prev_user, want)
-            bar_ok = first[s - 1] + K["bar_gap"] if s > 0 else -1                        # barrier(s-1) makes slab s visible
-            rel = max(rel, bar_ok + 1) if K["bar"] else rel
-            base, off = frag_addr(s, ks)
-            add(Filler("ds_read_b128 v[%d:%d], %s offset:%d" % (ring(kidx), ring(kidx) + 3, base, off), K["lds_cost"], rel,
-                       use - 1, "ds_read", tag=("frag", kidx)))
-
-    # ---- bias of slab s: 4 x ds_read_b128 into v[192:207]; free once k-step 0 of slab s-1 has issued (+2 MFMAs) ----------
+def add_bias(P, sched):
+    """bias of slab s: 4 x ds_read_b128 into v[192:207]; free once k-step 0 of slab s-1 has issued (+2 MFMAs)"""
+    first = P.bb.first
     for s in range(1, N_SLABS_TRUNK):
         rel = first[s - 1] + 3
         dl = first[s] - 1
@@ -360,446 +200,297 @@ def gen(knobs):
         span = max(1, (first[s] - 1) - rel)
         for q in range(4):
             r = max(rel, first[s] - 10 + 2 * q) if span > 10 else rel
-            add(Filler("ds_read_b128 v[%d:%d], %%[vb] offset:%d" % (BIAS + 4 * q, BIAS + 4 * q + 3, s * 128 + q * 16),
-                       K["lds_cost"], r, dl, "ds_read", tag=("bias", s)))
+            sched.add(S.Filler(bias_read(s, q), P.K["lds_cost"], r, dl, "ds_read", tag=("bias", s)))
 
-    # ---- epilogue of slab s, run inside slab s+1 (the last one is flushed after the backbone) ---------------------------
-    # items: (kind, text, writes, tag, cls[, reads]);  cls "acc" = reads the slab's accumulator set (deadline: before slab s+2
-    # overwrites it), "post" = works on packed words / LDS / memory only (deadline one slab later; same-deadline items keep their
-    # program order, so a slab's post items still run before the next slab's accumulator items)
-    def store_epilogue(s):
-        L, t = layer_of(s), s % 8
-        W, st = WRITE_SET[L], s & 1
-        relu, sigma, copy = L <= 6, L == 7, L == 8
-        PKR = lambda pt, n: ACC(st, pt) + n              # packed word n of the point tile: over accumulator blocks 0, 1
-        # block i of a point tile -> its two packed words; after the swaps PK[0:3] = chunk e=0, PK[4:7] = chunk e=1 of the lane
-        slot_of = {0: (0, 1), 2: (2, 3), 1: (4, 5), 3: (6, 7)}
-        sigw = lambda i: SIGW + 4 * (i & 1)
-        items = []
-        def sig_load(i):
-            items.append(("ds_read", "ds_read_b128 v[%d:%d], v%d offset:%d" % (sigw(i), sigw(i) + 3, ST_VS, (16 * t + 4 * i) * 4), (), ("sigw", s, i), "acc"))
-        step = [0]
-        def sign(word):
-            if step[0] == 0:
-                items.append(("valu", "v_and_b32 v%d, %%[sm], v%d" % (ST_SB, word), (ST_SB,), None, "acc"))
-            else:
-                items.append(("valu", "v_lshrrev_b32 v%d, 1, v%d" % (ST_SB, ST_SB), (ST_SB,), None, "acc"))
-                items.append(("valu", "v_and_or_b32 v%d, v%d, %%[sm], v%d" % (ST_SB, word, ST_SB), (ST_SB,), None, "acc"))
-            step[0] += 1
-        def block(pt, i):
-            a = ACC(st, pt) + 4 * i
-            t0, t1 = PKR(pt, slot_of[i][0]), PKR(pt, slot_of[i][1])
-            q = 2 * i
-            r0 = act_reg(W, 2 * t + (q >> 2), pt) + (q & 3)
-            if sigma:
-                # layer 8: signs from the packed raw values, sigma head from the fp32 ReLU outputs (nerf.py:136, as in inference),
-                # ReLU of the packed pair lands in the point tile's packed-word registers (pk_max(cvt(x), 0) == cvt(max(x, 0)))
-                c0, c1 = ST_T0, ST_T0 + 1
-                items.append(("valu", "v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (c0, a, a + 1), (c0,), None, "acc"))
-                items.append(("valu", "v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (c1, a + 2, a + 3), (c1,), None, "acc"))
-                sign(c0); sign(c1)
-                for e in range(4):
-                    items.append(("valu", "v_max_f32 v%d, 0, v%d" % (a + e, a + e), (a + e,), None, "acc"))
-                for e in range(4):
-                    items.append(("valu", "v_fmac_f32 %%[sg%d], v%d, v%d" % (pt, sigw(i) + e, a + e), (), ("sigw", s, i), "acc"))
-                items.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t0, c0), (t0,), None, "acc"))
-                items.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t1, c1), (t1,), None, "acc"))
-            else:
-                items.append(("valu", "v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (t0, a, a + 1), (t0,), None, "acc"))
-                items.append(("valu", "v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (t1, a + 2, a + 3), (t1,), None, "acc"))
-                if not copy:
-                    sign(t0)
-                    items.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t0, t0), (t0,), None, "acc"))
-                    sign(t1)
-                    items.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t1, t1), (t1,), None, "acc"))
-            items.append(("valu", "v_accvgpr_write_b32 a%d, v%d" % (r0, t0), (("a", r0),), None, "acc"))
-            items.append(("valu", "v_accvgpr_write_b32 a%d, v%d" % (r0 + 1, t1), (("a", r0 + 1),), None, "acc"))
-        fin = []                                             # packed words -> staging planes (both point tiles), behind everything else
-        def finish_pt(pt):
-            pairs = [(PKR(pt, 0), PKR(pt, 2)), (PKR(pt, 1), PKR(pt, 3)), (PKR(pt, 4), PKR(pt, 6)), (PKR(pt, 5), PKR(pt, 7))]
-            for x, y in pairs:
-                if K["swap_rev"]:
-                    x, y = y, x
-                fin.append(("swap", "v_permlane32_swap_b32 v%d, v%d" % (x, y), (x, y), None, "acc", (x, y)))
-            for e in range(2):
-                off = pt * ST_PT + (t & 1) * ST_B3 + e * ST_E
-                if K["abl_stw"]:
-                    fin.append(("ds_write", "ds_write_b128 %%[stw], v[%d:%d] offset:%d" % (PKR(pt, 4 * e), PKR(pt, 4 * e) + 3, off), (), None, "acc"))
-        if sigma:                                            # q outermost, both point tiles share a quad's sigma weights
-            sig_load(0); sig_load(1)
-            for i in range(4):
-                for pt in range(2):
-                    block(pt, i)
-                if i + 2 < 4:
-                    sig_load(i + 2)
-        else:                                                # point tile outermost: the sign-word step order of the chain
-            for pt in range(2):
-                for i in range(4):
-                    block(pt, i)
-        finish_pt(0); finish_pt(1)
-        if not copy and K["abl_sign4"]:
-            if t % 4 == 3:
-                items.append(("vstore", "global_store_dwordx4 v%d, v[%d:%d], s[%d:%d] nt" % (ST_VSG, ST_SB, ST_SB + 3, ST_SGPR_SIGN, ST_SGPR_SIGN + 1), (), None, "post",
-                              (ST_SGPR_SIGN, ST_SGPR_SIGN + 1)))
-        elif not copy:                                       # the tile's ReLU sign word: 256 contiguous bytes per wave
-            items.append(("vstore", "global_store_dword v%d, v%d, s[%d:%d] nt" % (ST_VSG, ST_SB, ST_SGPR_SIGN, ST_SGPR_SIGN + 1), (), None, "post",
-                          (ST_SGPR_SIGN, ST_SGPR_SIGN + 1)))
-            items.append(("valu", "v_add_u32 v%d, 512, v%d" % (ST_VSG, ST_VSG), (ST_VSG,), None, "post"))
-        readout = []
-        if t & 1:                                            # tiles t-1, t of both point tiles leave as whole 128-byte rows
-            main_items, items = items, readout
-            tp = t >> 1
-            rows = [(pt, i) for pt in range(2) for i in range(4)]
-            def rd(n):
-                pt, i = rows[n]
-                ro = ST_RO + 4 * (n % 2)
-                src = "v%d" % ST_STR1 if (i & 1) else "%[str0]"
-                if K["abl_str"]:
-                    items.append(("ds_read", "ds_read_b128 v[%d:%d], %s offset:%d" % (ro, ro + 3, src, pt * ST_PT + 256 * i), (), ("ro", s, n), "post"))
-            def stw(n):
-                ro = ST_RO + 4 * (n % 2)
-                rokey = ("ro", s, n) if K["abl_str"] else None
-                if K["abl_vstore"]:
-                    items.append(("vstore", "global_store_dwordx4 %%[vo], v[%d:%d], s[%d:%d] offset:%d%s" % (ro, ro + 3, ST_SGPR_ACTS, ST_SGPR_ACTS + 1, 128 * tp, " nt" if K["nt"] else ""),
-                                  (), rokey, "post", (ST_SGPR_ACTS, ST_SGPR_ACTS + 1)))
-                else:                                        # timing ablation: the staged row is still waited for, nothing leaves
-                    items.append(("valu", "s_nop 0", (), rokey, "post"))
-                if n < 7:
-                    items.append(("valu", "v_add_u32 %[vo], 4096, %[vo]", ("vo",), None, "post"))
-                else:
-                    items.append(("valu", "v_subrev_u32 %[vo], 28672, %[vo]", ("vo",), None, "post"))
-            rd(0); rd(1)
-            for n in range(8):
-                stw(n)
-                if n + 2 < 8:
-                    rd(n + 2)
-            if t == 7:                                       # next layer: acts[L + 1]
-                items.append(("salu", "s_add_u32 s%d, s%d, %%[srlo]" % (ST_SGPR_ACTS, ST_SGPR_ACTS), (ST_SGPR_ACTS,), None, "post"))
-                items.append(("salu", "s_addc_u32 s%d, s%d, %%[srhi]" % (ST_SGPR_ACTS + 1, ST_SGPR_ACTS + 1), (ST_SGPR_ACTS + 1,), None, "post"))
-            items = main_items
-        if not K["abl_stage"]:
-            fin, readout = [], []
-        if not K["abl_sign"]:
-            items = [it for it in items if ("v%d" % ST_SB) not in it[1]]
-        return items, fin, readout
 
-    def interleave(a, b):
-        """deal list b evenly into list a (both keep their own order)"""
-        if not b:
-            return list(a)
-        out, j = [], 0
-        for i, x in enumerate(a):
-            out.append(x)
-            while j < len(b) and (j + 1) * len(a) <= (i + 1) * len(b):
-                out.append(b[j]); j += 1
-        return out + b[j:]
-
-    def store_flat(s):
-        """epilogue stream of slab s in store mode.  The row stores of a finished tile PAIR are not issued as a burst behind the odd
-        tile's epilogue: they are dealt evenly into the NEXT (even) tile's epilogue, in front of its staging writes (which re-use
-        the planes) -- one store per ~4 MFMAs instead of eight within a few gaps.  A wave whose store cannot issue (the CU's address
-        path is full) cannot issue its MFMAs either: without the staging round trip the kernel ran 0.51 ms, with it 0.72."""
-        items, fin, readout = store_epilogue(s)
-        prev = store_epilogue(s - 1)[2] if (s > 0 and K["spread"]) else []
-        out = interleave(items, prev) + fin
-        if not K["spread"] or s == N_SLABS_TRUNK - 1:
-            out += readout                                   # (the last pair of the trunk: behind the backbone)
-        return out
-
-    def plain_epilogue(s):
-        L, t = layer_of(s), s % 8
-        W = WRITE_SET[L]
-        st = s & 1
-        sigma = (L == 7) and K["sigma"]
-        copy = (L == 8)
-        groups = []
-        sigw = lambda i: SIGW + 4 * (i & 1)
-        def sig_load(i):                                 # sigma-head weights of quad i of this tile (both point tiles share them)
-            return [("ds_read", "ds_read_b128 v[%d:%d], %%[vs] offset:%d" % (sigw(i), sigw(i) + 3, (16 * t + 4 * i) * 4), (), ("sigw", s, i), "acc")]
+# ---- epilogue of slab s, run inside slab s+1 (the last one is flushed after the backbone): items as class Scheduler takes them ----
+def store_epilogue(P, s):
+    K, cvt = P.K, P.cvt
+    L, t = layer_of(s), s % 8
+    W, st = WRITE_SET[L], s & 1
+    sigma, copy = L == 7, L == 8
+    PKR = lambda pt, n: ACC(st, pt) + n              # packed word n of the point tile: over accumulator blocks 0, 1
+    # block i of a point tile -> its two packed words; after the swaps PK[0:3] = chunk e=0, PK[4:7] = chunk e=1 of the lane
+    slot_of = {0: (0, 1), 2: (2, 3), 1: (4, 5), 3: (6, 7)}
+    sigw = lambda i: SIGW + 4 * (i & 1)
+    items = []
+    def sig_load(i):
+        items.append(("ds_read", "ds_read_b128 v[%d:%d], v%d offset:%d" % (sigw(i), sigw(i) + 3, ST_VS, (16 * t + 4 * i) * 4), (), ("sigw", s, i), "acc"))
+    step = [0]
+    def sign(word):
+        if step[0] == 0:
+            items.append(("valu", "v_and_b32 v%d, %%[sm], v%d" % (ST_SB, word), (ST_SB,), None, "acc"))
+        else:
+            items.append(("valu", "v_lshrrev_b32 v%d, 1, v%d" % (ST_SB, ST_SB), (ST_SB,), None, "acc"))
+            items.append(("valu", "v_and_or_b32 v%d, v%d, %%[sm], v%d" % (ST_SB, word, ST_SB), (ST_SB,), None, "acc"))
+        step[0] += 1
+    def block(pt, i):
+        a = ACC(st, pt) + 4 * i
+        t0, t1 = PKR(pt, slot_of[i][0]), PKR(pt, slot_of[i][1])
+        q = 2 * i
+        r0 = act_reg(W, 2 * t + (q >> 2), pt) + (q & 3)
         if sigma:
-            groups.append(sig_load(0)); groups.append(sig_load(1))
+            # layer 8: signs from the packed raw values, sigma head from the fp32 ReLU outputs (nerf.py:136, as in inference),
+            # ReLU of the packed pair lands in the point tile's packed-word registers (pk_max(cvt(x), 0) == cvt(max(x, 0)))
+            c0, c1 = ST_T0, ST_T0 + 1
+            items.append(("valu", "%s v%d, v%d, v%d" % (cvt, c0, a, a + 1), (c0,), None, "acc"))
+            items.append(("valu", "%s v%d, v%d, v%d" % (cvt, c1, a + 2, a + 3), (c1,), None, "acc"))
+            sign(c0); sign(c1)
+            for e in range(4):
+                items.append(("valu", "v_max_f32 v%d, 0, v%d" % (a + e, a + e), (a + e,), None, "acc"))
+            for e in range(4):
+                items.append(("valu", "v_fmac_f32 %%[sg%d], v%d, v%d" % (pt, sigw(i) + e, a + e), (), ("sigw", s, i), "acc"))
+            items.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t0, c0), (t0,), None, "acc"))
+            items.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t1, c1), (t1,), None, "acc"))
+        else:
+            items.append(("valu", "%s v%d, v%d, v%d" % (cvt, t0, a, a + 1), (t0,), None, "acc"))
+            items.append(("valu", "%s v%d, v%d, v%d" % (cvt, t1, a + 2, a + 3), (t1,), None, "acc"))
+            if not copy:
+                sign(t0)
+                items.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t0, t0), (t0,), None, "acc"))
+                sign(t1)
+                items.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t1, t1), (t1,), None, "acc"))
+        items.append(("valu", "v_accvgpr_write_b32 a%d, v%d" % (r0, t0), (("a", r0),), None, "acc"))
+        items.append(("valu", "v_accvgpr_write_b32 a%d, v%d" % (r0 + 1, t1), (("a", r0 + 1),), None, "acc"))
+    fin = []                                             # packed words -> staging planes (both point tiles), behind everything else
+    def finish_pt(pt):
+        pairs = [(PKR(pt, 0), PKR(pt, 2)), (PKR(pt, 1), PKR(pt, 3)), (PKR(pt, 4), PKR(pt, 6)), (PKR(pt, 5), PKR(pt, 7))]
+        for x, y in pairs:
+            if K["swap_rev"]:
+                x, y = y, x
+            fin.append(("swap", "v_permlane32_swap_b32 v%d, v%d" % (x, y), (x, y), None, "acc", (x, y)))
+        for e in range(2):
+            off = pt * ST_PT + (t & 1) * ST_B3 + e * ST_E
+            if K["abl_stw"]:
+                fin.append(("ds_write", "ds_write_b128 %%[stw], v[%d:%d] offset:%d" % (PKR(pt, 4 * e), PKR(pt, 4 * e) + 3, off), (), None, "acc"))
+    if sigma:                                            # q outermost, both point tiles share a quad's sigma weights
+        sig_load(0); sig_load(1)
         for i in range(4):
             for pt in range(2):
-                a = ACC(st, pt) + 4 * i
-                t0, t1 = TMP0 + 2 * ((2 * i + pt) % K["tmp_pairs"]), TMP0 + 2 * ((2 * i + pt) % K["tmp_pairs"]) + 1
-                q = 2 * i
-                r0 = act_reg(W, 2 * t + (q >> 2), pt) + (q & 3)
-                ins = []
-                if sigma:
-                    for e in range(4):
-                        ins.append(("valu", "v_max_f32 v%d, 0, v%d" % (a + e, a + e), (a + e,), None, "acc"))
-                    for e in range(4):
-                        ins.append(("valu", "v_fmac_f32 %%[sg%d], v%d, v%d" % (pt, sigw(i) + e, a + e), (), ("sigw", s, i), "acc"))
-                    ins.append(("valu", "v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (t0, a, a + 1), (t0,), None, "acc"))
-                    ins.append(("valu", "v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (t1, a + 2, a + 3), (t1,), None, "acc"))
-                else:
-                    ins.append(("valu", "v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (t0, a, a + 1), (t0,), None, "acc"))
-                    ins.append(("valu", "v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (t1, a + 2, a + 3), (t1,), None, "acc"))
-                    if not copy:
-                        ins.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t0, t0), (t0,), None, "acc"))
-                        ins.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t1, t1), (t1,), None, "acc"))
-                ins.append(("valu", "v_accvgpr_write_b32 a%d, v%d" % (r0, t0), (("a", r0),), None, "acc"))
-                ins.append(("valu", "v_accvgpr_write_b32 a%d, v%d" % (r0 + 1, t1), (("a", r0 + 1),), None, "acc"))
-                groups.append(ins)
-            if sigma and i + 2 < 4:                      # the buffer quad i used is free once its fmacs have issued (in order)
-                groups.append(sig_load(i + 2))
-        return [x for grp in groups for x in grp]
+                block(pt, i)
+            if i + 2 < 4:
+                sig_load(i + 2)
+    else:                                                # point tile outermost: the sign-word step order of the chain
+        for pt in range(2):
+            for i in range(4):
+                block(pt, i)
+    finish_pt(0); finish_pt(1)
+    if not copy and K["abl_sign4"]:
+        if t % 4 == 3:
+            items.append(("vstore", "global_store_dwordx4 v%d, v[%d:%d], s[%d:%d] nt" % (ST_VSG, ST_SB, ST_SB + 3, ST_SGPR_SIGN, ST_SGPR_SIGN + 1), (), None, "post",
+                          (ST_SGPR_SIGN, ST_SGPR_SIGN + 1)))
+    elif not copy:                                       # the tile's ReLU sign word: 256 contiguous bytes per wave
+        items.append(("vstore", "global_store_dword v%d, v%d, s[%d:%d] nt" % (ST_VSG, ST_SB, ST_SGPR_SIGN, ST_SGPR_SIGN + 1), (), None, "post",
+                      (ST_SGPR_SIGN, ST_SGPR_SIGN + 1)))
+        items.append(("valu", "v_add_u32 v%d, 512, v%d" % (ST_VSG, ST_VSG), (ST_VSG,), None, "post"))
+    readout = store_readout(K, s) if t & 1 else []
+    if not K["abl_stage"]:
+        fin, readout = [], []
+    if not K["abl_sign"]:
+        items = [it for it in items if ("v%d" % ST_SB) not in it[1]]
+    return items, fin, readout
 
-    COST = {"ds_read": K["lds_cost"], "ds_write": K["lds_cost"], "valu": K["valu_cost"], "swap": K["valu_cost"],
-            "vstore": K["dma_cost"], "salu": K["salu_cost"]}
-    def as_filler(item, rel, dl):
-        kind, text, writes, tag, _cls = item[:5]
-        reads = item[5] if len(item) > 5 else ()
-        return Filler(text, COST[kind], rel, dl, kind, reads=reads, writes=writes, tag=tag)
 
-    epi_tail = []
-    epi_fillers = []
-    for s in range(N_SLABS_TRUNK):
-        if not K["epi"]:
-            break
-        L, t = layer_of(s), s % 8
-        if s + 1 < N_SLABS_TRUNK:
-            rel0 = first[s + 1] + 1                      # two MFMAs after the slab's last one: results readable
-            n_gaps = first[s + 2] - first[s + 1] if s + 2 <= N_SLABS_TRUNK else 32
-            hard_dl = first[s + 2] - 1 if s + 2 < N_SLABS_TRUNK else len(mf) - 1   # accumulator set is overwritten by slab s+2
-            post_dl = first[s + 3] - 1 if s + 3 < N_SLABS_TRUNK else len(mf) - 1
+def store_readout(K, s):
+    """store mode, odd tile: tiles t-1, t of both point tiles leave the staging planes as whole 128-byte rows"""
+    t = s % 8
+    tp = t >> 1
+    items = []
+    rows = [(pt, i) for pt in range(2) for i in range(4)]
+    def rd(n):
+        pt, i = rows[n]
+        ro = ST_RO + 4 * (n % 2)
+        src = "v%d" % ST_STR1 if (i & 1) else "%[str0]"
+        if K["abl_str"]:
+            items.append(("ds_read", "ds_read_b128 v[%d:%d], %s offset:%d" % (ro, ro + 3, src, pt * ST_PT + 256 * i), (), ("ro", s, n), "post"))
+    def stw(n):
+        ro = ST_RO + 4 * (n % 2)
+        rokey = ("ro", s, n) if K["abl_str"] else None
+        if K["abl_vstore"]:
+            items.append(("vstore", "global_store_dwordx4 %%[vo], v[%d:%d], s[%d:%d] offset:%d%s" % (ro, ro + 3, ST_SGPR_ACTS, ST_SGPR_ACTS + 1, 128 * tp, " nt" if K["nt"] else ""),
+                          (), rokey, "post", (ST_SGPR_ACTS, ST_SGPR_ACTS + 1)))
+        else:                                        # timing ablation: the staged row is still waited for, nothing leaves
+            items.append(("valu", "s_nop 0", (), rokey, "post"))
+        if n < 7:
+            items.append(("valu", "v_add_u32 %[vo], 4096, %[vo]", ("vo",), None, "post"))
         else:
-            rel0 = None
-        flat = store_flat(s) if STORE else plain_epilogue(s)
-        if rel0 is None:
-            epi_tail = flat
-            continue
-        # deadline of the activation registers: the next layer reads k-steps 2t, 2t+1 of set W.  Only the LAST tile of a
-        # layer is read soon (k-steps 14, 15 of the next layer's first slab); everything else only has the accumulator
-        # deadline.
-        n = len(flat)
-        per_gap = max(2, -(-n // max(1, (n_gaps - 4))))
-        dl = hard_dl
-        if t == 7 and L + 1 <= 8:
-            nxt_first_slab = 8 * (L + 1)
-            ks_needed = (4 if nxt_first_slab == 32 else 0) + 14      # skip layer: 4 xe k-steps come first
-            dl = min(dl, idx_of[(nxt_first_slab, ks_needed, 0)] - 2)
-        for j, item in enumerate(flat):
-            rel = rel0 + j // per_gap
-            d = dl if item[4] == "acc" else max(dl, post_dl)
-            f = as_filler(item, min(rel, d), d)
-            add(f)
-            epi_fillers.append(f)
-    if STORE:
-        # the epilogue stream is ONE program-ordered sequence (packed-word registers, the sign word, the staging tile and the
-        # running store offset are reused from tile to tile): deadlines must not decrease along it, or the list scheduler
-        # (earliest deadline first) would let a later tile's conversions overtake an earlier tile's staging writes
-        for a, b in zip(reversed(epi_fillers[:-1]), reversed(epi_fillers[1:])):
-            if a.deadline > b.deadline:
-                a.deadline = b.deadline
-                a.release = min(a.release, a.deadline)
+            items.append(("valu", "v_subrev_u32 %[vo], 28672, %[vo]", ("vo",), None, "post"))
+    rd(0); rd(1)
+    for n in range(8):
+        stw(n)
+        if n + 2 < 8:
+            rd(n + 2)
+    if t == 7:                                       # next layer: acts[L + 1]
+        items.append(("salu", "s_add_u32 s%d, s%d, %%[srlo]" % (ST_SGPR_ACTS, ST_SGPR_ACTS), (ST_SGPR_ACTS,), None, "post"))
+        items.append(("salu", "s_addc_u32 s%d, s%d, %%[srhi]" % (ST_SGPR_ACTS + 1, ST_SGPR_ACTS + 1), (ST_SGPR_ACTS + 1,), None, "post"))
+    return items
 
-    # ---- barrier + weight stream: at slab s, barrier (slab s+1 visible), then DMA of slab s+3 ------------------------------
+
+def store_flat(P, s):
+    """epilogue stream of slab s in store mode.  The row stores of a finished tile PAIR are not issued as a burst behind the odd
+    tile's epilogue: they are dealt evenly into the NEXT (even) tile's epilogue, in front of its staging writes (which re-use
+    the planes) -- one store per ~4 MFMAs instead of eight within a few gaps.  A wave whose store cannot issue (the CU's address
+    path is full) cannot issue its MFMAs either: without the staging round trip the kernel ran 0.51 ms, with it 0.72."""
+    items, fin, readout = store_epilogue(P, s)
+    prev = store_epilogue(P, s - 1)[2] if (s > 0 and P.K["spread"]) else []
+    out = S.interleave(items, prev) + fin
+    if not P.K["spread"] or s == N_SLABS_TRUNK - 1:
+        out += readout                                   # (the last pair of the trunk: behind the backbone)
+    return out
+
+
+def plain_epilogue(P, s):
+    K, cvt = P.K, P.cvt
+    L, t = layer_of(s), s % 8
+    W = WRITE_SET[L]
+    st = s & 1
+    sigma = (L == 7) and K["sigma"]
+    copy = (L == 8)
+    groups = []
+    sigw = lambda i: SIGW + 4 * (i & 1)
+    def sig_load(i):                                 # sigma-head weights of quad i of this tile (both point tiles share them)
+        return [("ds_read", "ds_read_b128 v[%d:%d], %%[vs] offset:%d" % (sigw(i), sigw(i) + 3, (16 * t + 4 * i) * 4), (), ("sigw", s, i), "acc")]
+    if sigma:
+        groups.append(sig_load(0)); groups.append(sig_load(1))
+    for i in range(4):
+        for pt in range(2):
+            a = ACC(st, pt) + 4 * i
+            t0, t1 = TMP0 + 2 * ((2 * i + pt) % K["tmp_pairs"]), TMP0 + 2 * ((2 * i + pt) % K["tmp_pairs"]) + 1
+            q = 2 * i
+            r0 = act_reg(W, 2 * t + (q >> 2), pt) + (q & 3)
+            ins = []
+            if sigma:
+                for e in range(4):
+                    ins.append(("valu", "v_max_f32 v%d, 0, v%d" % (a + e, a + e), (a + e,), None, "acc"))
+                for e in range(4):
+                    ins.append(("valu", "v_fmac_f32 %%[sg%d], v%d, v%d" % (pt, sigw(i) + e, a + e), (), ("sigw", s, i), "acc"))
+            ins.append(("valu", "%s v%d, v%d, v%d" % (cvt, t0, a, a + 1), (t0,), None, "acc"))
+            ins.append(("valu", "%s v%d, v%d, v%d" % (cvt, t1, a + 2, a + 3), (t1,), None, "acc"))
+            if not sigma and not copy:
+                ins.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t0, t0), (t0,), None, "acc"))
+                ins.append(("valu", "v_pk_max_i16 v%d, v%d, 0" % (t1, t1), (t1,), None, "acc"))
+            ins.append(("valu", "v_accvgpr_write_b32 a%d, v%d" % (r0, t0), (("a", r0),), None, "acc"))
+            ins.append(("valu", "v_accvgpr_write_b32 a%d, v%d" % (r0 + 1, t1), (("a", r0 + 1),), None, "acc"))
+            groups.append(ins)
+        if sigma and i + 2 < 4:                      # the buffer quad i used is free once its fmacs have issued (in order)
+            groups.append(sig_load(i + 2))
+    return [x for grp in groups for x in grp]
+
+
+def add_epilogues(P, sched):
+    """Returns the last slab's epilogue (flushed behind the backbone).  The activation registers have a deadline of their own: the
+    next layer reads k-steps 2t, 2t+1 of the written set.  Only the LAST tile of a layer is read soon (k-steps 14, 15 of the next
+    layer's first slab); everything else only has the accumulator deadline."""
+    if not P.K["epi"]:
+        return []
+    def handover(s):
+        L, t = layer_of(s), s % 8
+        if t == 7 and L + 1 <= 8:
+            nxt = 8 * (L + 1)
+            return P.bb.idx_of[(nxt, (4 if nxt == 32 else 0) + 14, 0)]       # skip layer: 4 xe k-steps come first
+    flat_of = (lambda s: store_flat(P, s)) if P.store else (lambda s: plain_epilogue(P, s))
+    return sched.add_deferred_epilogues(P.bb, flat_of, 1, handover, program_order=P.store)
+
+
+def add_weight_stream(P, sched):
+    """barrier + weight stream: at slab s, barrier (slab s+1 visible), then the DMA pieces of staged_at(s)"""
+    K, first = P.K, P.bb.first
     for s in range(N_SLABS_TRUNK):
         b = first[s] + K["bar_gap"]
         if K["bar"]:
-            add(Filler("", 0.5, b, b, "bar", tag=s + 1))
-        if K["dma"]:
-            targets = staged_at(s, STORE)
-            plist = []                                    # (lds byte offset, goff bump, tag)
-            for tgt in targets:
-                real = tgt - 1000 if tgt >= 1000 else tgt
-                nbytes = slab_k(real) * 64
-                pieces = -(-nbytes // 4096)
-                slot = real % n_slots
-                for p in range(pieces):
-                    bump = min(4096, nbytes - p * 4096)
-                    if tgt >= 1000 and real == 0 and p == 0:
-                        bump = None                       # the stream wraps: goff restarts at tid*16 (+4096 behind this piece)
-                    plist.append((slot * SLOT_BYTES + p * 4096, bump, s + dma_dist if (tgt != 5 or STORE) else 5))
-            n_g = first[s + 1] - first[s]
-            gaps_avail = max(1, n_g - K["bar_gap"] - 3)
-            stride = max(1, gaps_avail // max(1, len(plist)))
-            if K["dma_early"]:
-                stride = 1
-            for p, (lds_off, bump, tag) in enumerate(plist):
-                rel = b + 1 + p * stride
-                dl = first[s + 1] - 1
-                add(Filler("s_add_u32 m0, %%[wv1k], %d" % lds_off, K["salu_cost"], min(rel, dl), dl, "m0"))
-                if bump is None:                  # back to the start of the blob: minus the whole weight stream (76 slabs)
-                    total = sum(slab_k(x) * 64 for x in range(N_SLABS))
-                    add(Filler("v_subrev_u32 %%[goff], %d, %%[goff]" % total, K["valu_cost"], min(rel, dl), dl, "valu", writes=("goff",)))
-                    bump = 4096
-                add(Filler("global_load_lds_dwordx4 %[goff], %[blob]", K["dma_cost"], min(rel, dl), dl, "dma", tag=tag))
-                add(Filler("v_add_u32 %%[goff], %d, %%[goff]" % bump, K["valu_cost"], min(rel, dl), dl, "valu", writes=("goff",)))
+            sched.add(S.Filler("", 0.5, b, b, "bar", tag=s + 1))
+        if not K["dma"]:
+            continue
+        plist = []                                    # (lds byte offset, goff bump, tag)
+        for tgt in staged_at(s, P.store):
+            real = tgt - 1000 if tgt >= 1000 else tgt
+            nbytes = slab_k(real) * 64
+            slot = real % P.n_slots
+            for p in range(-(-nbytes // 4096)):
+                bump = min(4096, nbytes - p * 4096)
+                if tgt >= 1000 and real == 0 and p == 0:
+                    bump = None                       # the stream wraps: goff restarts at tid*16 (+4096 behind this piece)
+                plist.append((slot * SLOT_BYTES + p * 4096, bump, s + P.dma_dist if (tgt != 5 or P.store) else 5))
+        gaps_avail = max(1, first[s + 1] - first[s] - K["bar_gap"] - 3)
+        stride = 1 if K["dma_early"] else max(1, gaps_avail // max(1, len(plist)))
+        dl = first[s + 1] - 1
+        for p, (lds_off, bump, tag) in enumerate(plist):
+            rel = min(b + 1 + p * stride, dl)
+            if bump is None:                          # back to the start of the blob: minus the whole weight stream (76 slabs)
+                sched.weight_stream_piece("s_add_u32 m0, %%[wv1k], %d" % lds_off, rel, dl, tag,
+                                          rewind=sum(slab_k(x) * 64 for x in range(N_SLABS)))
+            else:
+                sched.weight_stream_piece("s_add_u32 m0, %%[wv1k], %d" % lds_off, rel, dl, tag, bump=bump)
 
-    # ---- emission -----------------------------------------------------------------------------------------------------
-    fillers.sort(key=lambda f: (f.release, f.seq))
-    pending = []          # released, not yet emitted (kept in seq order within equal deadlines)
-    fi = 0
-    if K["setprio"]:
-        g.emit("s_setprio %d" % K["setprio"])
-    # preamble: address registers, first D fragments + bias of slab 0
+
+def preamble(P, g):
+    """address registers, first D fragments + bias of slab 0"""
     g.emit("v_add_u32 v%d, %d, %%[va0]" % (VA1, SLOTS_PER_BASE * SLOT_BYTES))
-    if not STORE:
+    if not P.store:
         g.emit("v_add_u32 v%d, %d, %%[va0]" % (VA2, 2 * SLOTS_PER_BASE * SLOT_BYTES))
     else:                                                # running pointers of the statement (physical SGPRs, declared as clobbers)
         for dst, src in ((ST_SGPR_ACTS, "aplo"), (ST_SGPR_ACTS + 1, "aphi"), (ST_SGPR_SIGN, "sglo"), (ST_SGPR_SIGN + 1, "sghi")):
-            g.emit("s_mov_b32 s%d, %%[%s]" % (dst, src))
-            g.last_salu_write[dst] = g.n_states - 1
+            g.salu_mov(dst, "%%[%s]" % src)
         # lane addresses derived from the kernel's: vb = TAIL + 64 h -> sigma weights at TAIL + 4 (BIAS_FLOATS + 128 h) = 8 vb - 7 TAIL
         # + 4 BIAS_FLOATS (%[vsk] = that constant); the odd-row staging read address = a copy of str0; the sign-store offset = lane * 4
         g.emit("v_lshl_add_u32 v%d, %%[vb], 3, %%[vsk]" % ST_VS)
         g.emit("v_mov_b32 v%d, %%[str0]" % ST_STR1)
         g.emit("v_lshrrev_b32 v%d, 2, %%[va0]" % ST_VSG)
     for q in range(4):
-        g.emit("ds_read_b128 v[%d:%d], %%[vb] offset:%d" % (BIAS + 4 * q, BIAS + 4 * q + 3, q * 16)); g.lgkm.append(("bias", 0))
-    if K["frag"]:
-        for kidx in range(D):
-            s, ks = kstep_list[kidx]
-            base, off = frag_addr(s, ks)
-            g.emit("ds_read_b128 v[%d:%d], %s offset:%d" % (ring(kidx), ring(kidx) + 3, base, off)); g.lgkm.append(("frag", kidx))
+        g.ds_read(bias_read(0, q), ("bias", 0))
+    if P.K["frag"]:
+        for kidx in range(P.D):
+            g.ds_read(frag_read(P, kidx), ("frag", kidx))
     else:
-        g.emit("ds_read_b128 v[%d:%d], %%[va0] offset:0" % (RING0, RING0 + 3)); g.lgkm.append(("frag", 0))
+        g.ds_read("ds_read_b128 v[%d:%d], %%[va0] offset:0" % (RING0, RING0 + 3), ("frag", 0))
 
-    def pop_ready(i):
-        """the gap behind MFMA i: pending fillers in (deadline, seq) order while the issue budget lasts.  STRICT order: the
-        first filler that does not fit closes the gap (dependent fillers -- m0 / DMA / address bump, cvt / max / write -- sit
-        next to each other in this order and must never overtake one another)."""
-        nonlocal pending
-        pending.sort(key=lambda f: (f.deadline, f.seq))
-        budget = K["cap"]
-        n = 0
-        for f in pending:
-            if budget < f.cost - 1e-9:
-                break
-            g.run_filler(f); budget -= f.cost; n += 1
-        pending = pending[n:]
 
-    for i, (s, ks, pt) in enumerate(mf):
-        # release
-        while fi < len(fillers) and fillers[fi].release <= i - 1:
-            pending.append(fillers[fi]); fi += 1
-        # forced fillers (deadline = before this MFMA)
-        pending.sort(key=lambda f: (f.deadline, f.seq))
-        keep = []
-        for f in pending:
-            if f.deadline <= i - 1:
-                g.run_filler(f); g.stats["forced"] += 1
-            else:
-                keep.append(f)
-        pending = keep
-        # operands
-        kidx = gk[(s, ks)]
-        kind, nx, na = slab_kind(s)
-        need = {("frag", kidx if K["frag"] else 0)}
-        if ks == 0:
-            need.add(("bias", s))
-        g.wait_lgkm(need)
-        a_reg = ring(kidx) if K["frag"] else RING0
-        st = s & 1
-        d = ACC(st, pt)
-        c = BIAS if ks == 0 else d
-        if ks < nx:
-            b_txt = "%%[xe%d]" % (ks * 2 + pt)
-            regs = ()
-        else:
-            rs = READ_SET[layer_of(s)]
-            b0 = act_reg(rs, ks - nx, pt)
-            b_txt = "a[%d:%d]" % (b0, b0 + 3)
-            regs = [("a", b0 + e) for e in range(4)]
-        g.pad_valu_to_mfma(regs)
-        g.emit("v_mfma_f32_32x32x16_bf16 v[%d:%d], v[%d:%d], %s, v[%d:%d]" % (d, d + 15, a_reg, a_reg + 3, b_txt, c, c + 15), states=8)
-        g.mfma_count += 1
-        # the gap behind this MFMA
-        while fi < len(fillers) and fillers[fi].release <= i:
-            pending.append(fillers[fi]); fi += 1
-        pop_ready(i)
+def issue_mfma(P, g, entry):
+    s, ks, pt = entry
+    frag = P.K["frag"]
+    kidx = P.bb.gk[(s, ks)]
+    nx = slab_kind(s)[1]
+    need = {("frag", kidx if frag else 0)}
+    if ks == 0:
+        need.add(("bias", s))
+    g.wait_lgkm(need)
+    a_reg = ring(P, kidx) if frag else RING0
+    d = ACC(s & 1, pt)
+    c = BIAS if ks == 0 else d                           # the bias enters as the C operand of the slab's first k-step
+    if ks < nx:
+        b_txt = "%%[xe%d]" % (ks * 2 + pt)
+    else:
+        b0 = act_reg(READ_SET[layer_of(s)], ks - nx, pt)
+        b_txt = "a[%d:%d]" % (b0, b0 + 3)
+        g.pad_valu_to_mfma([("a", b0 + e) for e in range(4)])
+    g.mfma("%s v[%d:%d], v[%d:%d], %s, v[%d:%d]" % (P.mfma, d, d + 15, a_reg, a_reg + 3, b_txt, c, c + 15))
 
-    # ---- tail: everything still pending, the last slab's epilogue (MFMA results: 11 wait states), drain --------------------
-    while fi < len(fillers):
-        pending.append(fillers[fi]); fi += 1
-    pending.sort(key=lambda f: (f.deadline, f.seq))
-    for f in pending:
-        g.run_filler(f)
-    g.nop(12)
-    for item in epi_tail:
-        g.run_filler(as_filler(item, 0, 0))
-    if g.lgkm:
-        g.emit("s_waitcnt lgkmcnt(0)")
-        g.lgkm = []
+
+def gen(knobs):
+    K, P = knobs, plan(knobs)
+    # LDS-DMA pieces that may be in flight on entry: at most the single pieces of slabs 1..4, issued by the previous tile's
+    # dir_encoding section / the prologue; store mode (distance 3): slabs 1, 2
+    g = S.Emitter([1, 2] if K["store"] else [1, 2, 3, 4], dma_thin=K["dma_thin"], dma_exec=K["dma_exec"])
+    sched = S.Scheduler(g, K["dma_cost"], K["valu_cost"], K["lds_cost"], K["salu_cost"])
+    add_fragments(P, sched)
+    add_bias(P, sched)
+    epi_tail = add_epilogues(P, sched)
+    add_weight_stream(P, sched)
+    if K["setprio"]:
+        g.emit("s_setprio %d" % K["setprio"])
+    preamble(P, g)
+    sched.run(P.bb.mf, lambda i, entry: issue_mfma(P, g, entry), K["cap"])
+    sched.finish(12, epi_tail)                           # MFMA results: 11 wait states
     g.nop(2)                                             # accvgpr_write -> the compiler's first dir_encoding MFMA
     if K["setprio"]:
         g.emit("s_setprio 0")
     return g
 
 
-def write_inc(out_path, g, prefix, header, v_first=V_FIRST):
-    """the emitted stream as a C string macro <prefix>_ASM + the clobber list <prefix>_CLOBBERS (every physical register the text
-    names, and the whole AGPR file)"""
-    import re
-    n_other = len(g.out) - g.mfma_count
-    with open(out_path, "w") as f:
-        f.write("// GENERATED by %s -- do not edit.\n" % header)
-        f.write("// %d MFMAs, %d other instructions (%.2f per MFMA): %d s_nop, %d counted waits\n"
-                % (g.mfma_count, n_other, n_other / g.mfma_count, g.stats["nop"], g.stats["wait"]))
-        f.write("#define %s_ASM \\\n" % prefix)
-        for line in g.out:
-            f.write('  "%s\\n\\t" \\\n' % line)
-        f.write('  ""\n')
-        used, sused = set(), set()
-        for line in g.out:
-            for m in re.finditer(r"\bv\[(\d+):(\d+)\]", line):
-                used.update(range(int(m.group(1)), int(m.group(2)) + 1))
-            for m in re.finditer(r"\bv(\d+)\b", line):
-                used.add(int(m.group(1)))
-            for m in re.finditer(r"\bs\[(\d+):(\d+)\]", line):
-                sused.update(range(int(m.group(1)), int(m.group(2)) + 1))
-            for m in re.finditer(r"\bs(\d+)\b", line):
-                sused.add(int(m.group(1)))
-        assert used and min(used) >= v_first, "the statement only names registers of its own range"
-        f.write("#define %s_CLOBBERS " % prefix + ", ".join('"v%d"' % r for r in sorted(used)) + ", "
-                + "".join('"s%d", ' % r for r in sorted(sused))
-                + ", ".join('"a%d"' % r for r in range(256)) + ', "memory", "scc"\n')
-
-
 def main():
-    out_path = sys.argv[1]
-    knobs = dict(KNOBS)
-    for kv in sys.argv[2:]:
-        k, v = kv.split("=")
-        knobs[k] = type(KNOBS[k])(float(v)) if isinstance(KNOBS[k], float) else int(v)
-    g = gen(knobs)
-    if knobs.get("f16"):
-        g.out = [l.replace("v_cvt_pk_bf16_f32", "v_cvt_pk_f16_f32").replace("v_mfma_f32_32x32x16_bf16", "v_mfma_f32_32x32x16_f16") for l in g.out]
-    n_other = len(g.out) - g.mfma_count
-    with open(out_path, "w") as f:
-        f.write("// GENERATED by tools/gen_bf16_trunk.py %s -- do not edit.\n" % " ".join(sys.argv[2:]))
-        f.write("// %d MFMAs, %d other instructions (%.2f per MFMA): %d s_nop, %d counted waits\n"
-                % (g.mfma_count, n_other, n_other / g.mfma_count, g.stats["nop"], g.stats["wait"]))
-        f.write("#define SN_BF16_TRUNK_ASM \\\n")
-        for line in g.out:
-            f.write('  "%s\\n\\t" \\\n' % line)
-        f.write('  ""\n')
-        # the statement overwrites the WHOLE hand-managed AGPR file: declared, so that the compiler can never park a value in an
-        # AGPR across it (under register pressure it otherwise hoists loop invariants into a0.., which the next tile reads back
-        # after this statement has overwritten them -- tools/check_agpr.py flags any compiler-allocated AGPR for the same reason)
-        # VGPRs: exactly the physical registers the emitted text names (a shorter fragment ring etc. hands registers back to
-        # the compiler, which has to keep everything that lives across the statement in what is left of v0..v255)
-        import re
-        used = set()
-        for line in g.out:
-            for m in re.finditer(r"\bv\[(\d+):(\d+)\]", line):
-                used.update(range(int(m.group(1)), int(m.group(2)) + 1))
-            for m in re.finditer(r"\bv(\d+)\b", line):
-                used.add(int(m.group(1)))
-        assert used and min(used) >= V_FIRST, "the statement only names registers of its own range"
-        sused = set()
-        for line in g.out:
-            for m in re.finditer(r"\bs\[(\d+):(\d+)\]", line):
-                sused.update(range(int(m.group(1)), int(m.group(2)) + 1))
-            for m in re.finditer(r"\bs(\d+)\b", line):
-                sused.add(int(m.group(1)))
-        f.write("#define SN_BF16_TRUNK_CLOBBERS " + ", ".join('"v%d"' % r for r in sorted(used)) + ", "
-                + "".join('"s%d", ' % r for r in sorted(sused))
-                + ", ".join('"a%d"' % r for r in range(256)) + ', "memory", "scc"\n')
-    print("trunk: %d MFMAs, %d other (%.2f / MFMA), nops %d, waits %d, forced %d"
-          % (g.mfma_count, n_other, n_other / g.mfma_count, g.stats["nop"], g.stats["wait"], g.stats["forced"]))
+    g = gen(S.parse_knobs(sys.argv[2:], KNOBS))
+    S.write_inc(sys.argv[1], g, "SN_BF16_TRUNK", "tools/gen_bf16_trunk.py " + " ".join(sys.argv[2:]), v_first=V_FIRST)
+    print(S.summary_line("trunk", g))
 
 
 if __name__ == "__main__":

@@ -26,7 +26,11 @@ staged in half 0 / 1; md0 md1 (s) their LDS destinations + wave * 1024.
 
 usage: gen_dw_bf16.py out.inc
 """
+import os
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from mfma_stream import write_asm_macro      # noqa: E402
 
 F0 = 176                       # v[176:239]: two fragment sets of 8 x 4 registers
 T0 = 240                       # v[240:247]: read addresses of the chunk being gathered
@@ -103,18 +107,9 @@ def main():
     n_mfma = sum(1 for l in body if l.startswith("v_mfma"))
     with open(sys.argv[1], "w") as f:
         f.write("// GENERATED by tools/gen_dw_bf16.py -- do not edit.  %d MFMAs, %d other instructions per chunk pair.\n" % (n_mfma, len(body) - n_mfma))
-        f.write("#define SN_DWBF16_PAIR_ASM \\\n")
-        for l in body:
-            f.write('  "%s\\n\\t" \\\n' % l)
-        f.write('  ""\n')
-        f.write("#define SN_DWBF16_TAIL_ASM \\\n")
-        for l in gen_tail():
-            f.write('  "%s\\n\\t" \\\n' % l)
-        f.write('  ""\n')
-        f.write("#define SN_DWBF16_ZERO_ASM \\\n")
-        for i in range(256):
-            f.write('  "v_accvgpr_write_b32 a%d, 0\\n\\t" \\\n' % i)
-        f.write('  ""\n')
+        write_asm_macro(f, "SN_DWBF16_PAIR_ASM", body)
+        write_asm_macro(f, "SN_DWBF16_TAIL_ASM", gen_tail())
+        write_asm_macro(f, "SN_DWBF16_ZERO_ASM", ["v_accvgpr_write_b32 a%d, 0" % i for i in range(256)])
         f.write("#define SN_DWBF16_VGPR_CLOBBERS " + ", ".join('"v%d"' % r for r in list(range(F0, F0 + 64)) + list(range(T0, T0 + 8))) + "\n")
         f.write("#define SN_DWBF16_AGPR_CLOBBERS " + ", ".join('"a%d"' % r for r in range(256)) + "\n")
     print("dw bf16 chunk pair: %d MFMAs, %d other" % (n_mfma, len(body) - n_mfma))

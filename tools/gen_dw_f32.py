@@ -21,7 +21,11 @@ of the DMA pieces; ga gb (s, 64 bit) global bases of the chunk being staged; md 
 
 usage: gen_dw_f32.py out.inc
 """
+import os
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from mfma_stream import write_asm_macro      # noqa: E402
 
 F0 = 200                       # v[200:215]: fragment sets
 A_BYTES = 16 * 256 * 4         # A tile of a chunk (16 points x 256 features fp32); the B tile follows it
@@ -93,14 +97,8 @@ def main():
     n_mfma = sum(1 for l in body if l.startswith("v_mfma"))
     with open(sys.argv[1], "w") as f:
         f.write("// GENERATED by tools/gen_dw_f32.py -- do not edit.  %d MFMAs, %d other instructions per chunk.\n" % (n_mfma, len(body) - n_mfma))
-        f.write("#define SN_DWF32_CHUNK_ASM \\\n")
-        for l in body:
-            f.write('  "%s\\n\\t" \\\n' % l)
-        f.write('  ""\n')
-        f.write("#define SN_DWF32_ZERO_ASM \\\n")
-        for i in range(256):
-            f.write('  "v_accvgpr_write_b32 a%d, 0\\n\\t" \\\n' % i)
-        f.write('  ""\n')
+        write_asm_macro(f, "SN_DWF32_CHUNK_ASM", body)
+        write_asm_macro(f, "SN_DWF32_ZERO_ASM", ["v_accvgpr_write_b32 a%d, 0" % i for i in range(256)])
         f.write("#define SN_DWF32_FRAG_CLOBBERS " + ", ".join('"v%d"' % r for r in range(F0, F0 + 16)) + "\n")
         f.write("#define SN_DWF32_AGPR_CLOBBERS " + ", ".join('"a%d"' % r for r in range(256)) + "\n")
     print("dw f32 chunk: %d MFMAs, %d other" % (n_mfma, len(body) - n_mfma))

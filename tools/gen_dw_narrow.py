@@ -26,7 +26,11 @@ temporaries, v[120:127] raw fp32 B words (the compiler keeps v0..v47: two workgr
 
 usage: gen_dw_narrow.py out.inc
 """
+import os
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from mfma_stream import write_asm_macro      # noqa: E402
 
 F0, T0, RAW = 48, 112, 120                       # two waves per SIMD: a wave owns 256 of the 512 unified registers -- v0..v127 + a0..a127
 KB = 16
@@ -193,26 +197,13 @@ def main():
             sh = Shape(v)
             forms = [("W0", True)] + ([("WX", False)] if sh.two_forms else [])
             for tag, w0 in forms:
-                body = gen_pair(sh, w0)
-                f.write("#define SN_DWN%d_PAIR_%s_ASM \\\n" % (v, tag))
-                for l in body:
-                    f.write('  "%s\\n\\t" \\\n' % l)
-                f.write('  ""\n')
+                write_asm_macro(f, "SN_DWN%d_PAIR_%s_ASM" % (v, tag), gen_pair(sh, w0))
             if v in QUAD:
                 for tag, w0 in forms:
-                    f.write("#define SN_DWN%d_GROUP_%s_ASM \\\n" % (v, tag))
-                    for l in gen_group(sh, w0, QUAD[v]):
-                        f.write('  "%s\\n\\t" \\\n' % l)
-                    f.write('  ""\n')
+                    write_asm_macro(f, "SN_DWN%d_GROUP_%s_ASM" % (v, tag), gen_group(sh, w0, QUAD[v]))
                 f.write("#define SN_DWN%d_NCH %d\n" % (v, QUAD[v]))
-            f.write("#define SN_DWN%d_TAIL_ASM \\\n" % v)
-            for l in gen_tail(sh):
-                f.write('  "%s\\n\\t" \\\n' % l)
-            f.write('  ""\n')
-            f.write("#define SN_DWN%d_ZERO_ASM \\\n" % v)
-            for i in range(16 * sh.MT * sh.NT):
-                f.write('  "v_accvgpr_write_b32 a%d, 0\\n\\t" \\\n' % i)
-            f.write('  ""\n')
+            write_asm_macro(f, "SN_DWN%d_TAIL_ASM" % v, gen_tail(sh))
+            write_asm_macro(f, "SN_DWN%d_ZERO_ASM" % v, ["v_accvgpr_write_b32 a%d, 0" % i for i in range(16 * sh.MT * sh.NT)])
             f.write("#define SN_DWN%d_RING %d\n#define SN_DWN%d_BUF %d\n" % (v, sh.R, v, sh.BUF))
             n_mf = sum(l.startswith("v_mfma") for l in gen_pair(sh, True))
             print("dw narrow variant %d: %dx%d blocks/wave, ring %d x %d B, %d MFMAs + %d other per chunk pair"

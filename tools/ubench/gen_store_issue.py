@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bodies of tools/ubench/store_issue.hip: one loop iteration = 32 back-to-back bf16 MFMAs (a 'slab') with row stores dealt into the gaps.
    BODY_<name> macros; registers: a[0:63] accumulators, v[8:11] / v[12:15] operands, v[16:19] store data, v20 byte offset"""
+import os
 import sys
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from mfma_stream import write_asm_macro      # noqa: E402
 def body(n_st, kind="store", rot=False, solo=False):
     out = []
     for k in range(4):
@@ -31,7 +34,4 @@ def body(n_st, kind="store", rot=False, solo=False):
 with open(sys.argv[1], "w") as f:
     for name, b in [("NONE", body(0)), ("ST8", body(8)), ("ST4", body(4)), ("ST16", body(16)), ("ROT", body(8, rot=True)),
                     ("SOLO", body(8, solo=True)), ("LD8", body(8, kind="load"))]:
-        f.write("#define BODY_%s \\\n" % name)
-        for l in b:
-            f.write('  "%s\\n\\t" \\\n' % l)
-        f.write('  ""\n')
+        write_asm_macro(f, "BODY_%s" % name, b)
