@@ -22,7 +22,8 @@ extern "C" {
                             * 4: SN_DTYPE_BF16X3 (inference and training entries, packers), sn_pack_table_entries_dtype
                             * 5: SN_DTYPE_F16 (inference entries, packer), SN_FLAG_F32_LDS_RING
                             *    (additive within 5: the pose-gradient entries sn_ray_grads, sn_ray_grads_workspace_bytes,
-                            *    sn_composite_backward_rays, sn_generate_rays_backward and its workspace query) */
+                            *    sn_composite_backward_rays, sn_generate_rays_backward and its workspace query; the camera entries
+                            *    sn_generate_rays_cam, sn_generate_rays_cam_backward, sn_ndc_rays, sn_ndc_rays_backward) */
 
 #define SN_DTYPE_F32 0  /* v_mfma_f32_32x32x2_f32, exact fp32                                          */
 #define SN_DTYPE_BF16 1 /* v_mfma_f32_32x32x16_bf16, bf16 operands / fp32 accumulate                    */
@@ -316,6 +317,40 @@ int sn_generate_rays(const float* c2w, int H, int W, float focal, float near, fl
 long sn_generate_rays_backward_workspace_bytes(void);
 int sn_generate_rays_backward(const float* g_rays, int H, int W, float focal, int x0, int y0, int stride_x, int stride_y,
                               int patch_w, int patch_h, void* workspace, float* g_c2w, void* stream);
+
+/* ---- sn_generate_rays for the reference's other cameras.  datasets/ray_utils.py:89-91 + :109-114 (blender, llff) or
+ * datasets/dtu_proj.py:31-33 + ray_utils.py:109-114 (dtu), then optionally get_ndc_rays (datasets/ray_utils.py:144-162, the call
+ * sites llff_ray_patch_1image_proj.py:473-483, :541-545, :676-682), and the [o, d, near, far] packing.
+ * Camera direction of pixel (i, j):  convention 0 = ((i - cx) / fx, -(j - cy) / fy, -1);  convention 1 = ((i - cx) / fx, (j - cy) / fy, +1).
+ * ndc = 1: every ray goes through the NDC map of sn_ndc_rays with (H, W, ndc_focal, ndc_near) before it is written; ndc = 0: ndc_near
+ * is ignored, ndc_focal is still checked (pass fx).  near, far: columns 6, 7 as given (llff with NDC: 0, 1).  c2w, window, rays: as
+ * for sn_generate_rays, whose bits (convention 0, fx = fy = focal, cx = W/2, cy = H/2, ndc = 0) reproduces.
+ * SN_E_BADARG: convention or ndc not in {0, 1}; fx, fy or ndc_focal not finite or not positive.                              */
+int sn_generate_rays_cam(const float* c2w, int H, int W, float fx, float fy, float cx, float cy, int convention, int ndc,
+                         float ndc_focal, float ndc_near, float near, float far, int x0, int y0, int stride_x, int stride_y,
+                         int patch_w, int patch_h, float* rays, void* stream);
+
+/* ---- backward of sn_generate_rays_cam with respect to c2w: autograd of the lines above.  With ndc = 1 the gradient of each ray first
+ * goes back through the NDC map (as sn_ndc_rays_backward, at the world ray recomputed from c2w; no (n, 8) intermediate is written), then
+ * the 12 sums of sn_generate_rays_backward with this camera's directions.  c2w: 12 floats (DEVICE), read only when ndc = 1 (may be NULL
+ * otherwise).  workspace: sn_generate_rays_backward_workspace_bytes bytes.  Deterministic; with ndc = 0 and the camera of
+ * sn_generate_rays, the bits of sn_generate_rays_backward.                                                                   */
+int sn_generate_rays_cam_backward(const float* g_rays, const float* c2w, int H, int W, float fx, float fy, float cx, float cy,
+                                  int convention, int ndc, float ndc_focal, float ndc_near, int x0, int y0, int stride_x,
+                                  int stride_y, int patch_w, int patch_h, void* workspace, float* g_c2w, void* stream);
+
+/* ---- datasets/ray_utils.py:123-164 get_ndc_rays(H, W, focal, near, rays_o, rays_d) over rays that exist already: rays_in (n_rays, 8)
+ * [o, d, near, far] in world space -> rays_out (n_rays, 8) in NDC; columns 6, 7 are copied.  Computed op by op in the reference's
+ * order, one fp32 rounding per op; -1/(W/(2 focal)) and -1/(H/(2 focal)) are formed in double and cast once, as Python does.  A ray with
+ * d_z == 0 gives the reference's inf / NaN.  In place is allowed: rays_out may be rays_in.                                    */
+int sn_ndc_rays(const float* rays_in, long n_rays, int H, int W, float focal, float ndc_near, float* rays_out, void* stream);
+
+/* ---- backward of sn_ndc_rays: autograd of datasets/ray_utils.py:145-159 in fp32 with the forward intermediates recomputed from
+ * rays_in (the map's INPUT).  g_rays_out (n_rays, 8): gradient of the NDC rays (columns 6, 7 ignored) -> g_rays_in (n_rays, 8): gradient
+ * of the world rays, columns 6, 7 zero.  The shifted o_z is only approximately -near: its derivative terms are kept.
+ * g_rays_in must not overlap the inputs.                                                                                     */
+int sn_ndc_rays_backward(const float* rays_in, const float* g_rays_out, long n_rays, int H, int W, float focal, float ndc_near,
+                         float* g_rays_in, void* stream);
 
 /* ---- utils/__init__.py:19-21 (torch.optim.Adam, eps=1e-8) over one flat fp32 buffer (the all-reduce buffer).
  * step = 1-based iteration count (bias correction).                                                             */

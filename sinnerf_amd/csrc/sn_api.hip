@@ -429,6 +429,57 @@ int sn_generate_rays_backward(const float* g_rays, int H, int W, float focal, in
                                           (hipStream_t)stream);
 }
 
+// ---- cameras (fx, fy, cx, cy, sign convention) and the NDC map
+namespace {
+bool positive_finite(float v) { return v > 0.0f && v <= 3.402823466e38f; }                     // false for NaN and +inf
+// -1./(W/(2.*focal)), -1./(H/(2.*focal)) as Python forms them (datasets/ray_utils.py:153-158): in double, cast to fp32 once
+float ndc_scale(int size, float focal) { return (float)(-1.0 / ((double)size / (2.0 * (double)focal))); }
+
+int check_camera(int H, int W, float fx, float fy, int convention, int ndc, float ndc_focal, int x0, int y0, int stride_x, int stride_y,
+                 int patch_w, int patch_h) {
+  if (H < 1 || W < 1 || stride_x < 1 || stride_y < 1 || patch_w < 0 || patch_h < 0) return SN_E_BADARG;
+  if ((convention != 0 && convention != 1) || (ndc != 0 && ndc != 1)) return SN_E_BADARG;
+  if (!positive_finite(fx) || !positive_finite(fy) || !positive_finite(ndc_focal)) return SN_E_BADARG;
+  if (x0 < 0 || y0 < 0 || (patch_w > 0 && x0 + (patch_w - 1) * stride_x >= W) || (patch_h > 0 && y0 + (patch_h - 1) * stride_y >= H))
+    return SN_E_BADSHAPE;
+  return 0;
+}
+}  // namespace
+
+int sn_generate_rays_cam(const float* c2w, int H, int W, float fx, float fy, float cx, float cy, int convention, int ndc,
+                         float ndc_focal, float ndc_near, float near, float far, int x0, int y0, int stride_x, int stride_y,
+                         int patch_w, int patch_h, float* rays, void* stream) {
+  if (!c2w || !rays) return SN_E_BADARG;
+  if (const int refused = check_camera(H, W, fx, fy, convention, ndc, ndc_focal, x0, y0, stride_x, stride_y, patch_w, patch_h))
+    return refused;
+  return sn_generate_rays_cam_launch(c2w, fx, fy, cx, cy, convention, ndc, ndc_scale(W, ndc_focal), ndc_scale(H, ndc_focal), ndc_near,
+                                     near, far, x0, y0, stride_x, stride_y, patch_w, patch_h, rays, (hipStream_t)stream);
+}
+
+int sn_generate_rays_cam_backward(const float* g_rays, const float* c2w, int H, int W, float fx, float fy, float cx, float cy,
+                                  int convention, int ndc, float ndc_focal, float ndc_near, int x0, int y0, int stride_x,
+                                  int stride_y, int patch_w, int patch_h, void* workspace, float* g_c2w, void* stream) {
+  if (!g_rays || !workspace || !g_c2w) return SN_E_BADARG;
+  if (const int refused = check_camera(H, W, fx, fy, convention, ndc, ndc_focal, x0, y0, stride_x, stride_y, patch_w, patch_h))
+    return refused;
+  if (ndc && !c2w) return SN_E_BADARG;            // the NDC adjoint is taken at the world ray, which comes from c2w
+  return sn_generate_rays_cam_backward_launch(g_rays, c2w, fx, fy, cx, cy, convention, ndc, ndc_scale(W, ndc_focal),
+                                              ndc_scale(H, ndc_focal), ndc_near, x0, y0, stride_x, stride_y, patch_w, patch_h, workspace,
+                                              g_c2w, (hipStream_t)stream);
+}
+
+int sn_ndc_rays(const float* rays_in, long n_rays, int H, int W, float focal, float ndc_near, float* rays_out, void* stream) {
+  if (!rays_in || !rays_out || n_rays < 0 || H < 1 || W < 1 || !positive_finite(focal)) return SN_E_BADARG;
+  return sn_ndc_rays_launch(rays_in, n_rays, ndc_scale(W, focal), ndc_scale(H, focal), ndc_near, rays_out, (hipStream_t)stream);
+}
+
+int sn_ndc_rays_backward(const float* rays_in, const float* g_rays_out, long n_rays, int H, int W, float focal, float ndc_near,
+                         float* g_rays_in, void* stream) {
+  if (!rays_in || !g_rays_out || !g_rays_in || n_rays < 0 || H < 1 || W < 1 || !positive_finite(focal)) return SN_E_BADARG;
+  return sn_ndc_rays_backward_launch(rays_in, g_rays_out, n_rays, ndc_scale(W, focal), ndc_scale(H, focal), ndc_near, g_rays_in,
+                                     (hipStream_t)stream);
+}
+
 int sn_composite_forward(const float* raw, int has_rgb, const float* z_vals, const float* rays, const float* noise,
                          float noise_std, long n_rays, int n_samples, int white_back, float* rgb, float* depth,
                          float* weights, void* stream) {

@@ -6,6 +6,10 @@
 //   adam_kernel            utils/__init__.py:19-21 (torch.optim.Adam, eps=1e-8) over ONE flat parameter/gradient buffer
 //                          (the buffer the single RCCL all-reduce runs on): one elementwise launch per step.
 //   rays_bwd_*_kernel      the backward of generate_rays_kernel w.r.t. c2w (pose gradients): 12 deterministic sums over the rays.
+//   generate_rays_cam_kernel / rays_cam_bwd_partials_kernel / ndc_rays_kernel / ndc_rays_bwd_kernel
+//                          the two above for the reference's other cameras: separate fx, fy, a principal point and the OpenCV
+//                          signs of dtu (datasets/dtu_proj.py:17-35), and the NDC map of llff (datasets/ray_utils.py:123-164)
+//                          with its adjoint, fused into ray generation / the pose sums or over an existing (n, 8) ray array.
 //   loss_partials_kernel / loss_finish_kernel
 //                          the losses computed on the rendered rays right after the path: MSE coarse + fine
 //                          (losses.py:12-22, nn.MSELoss mean), SmoothL1 depth coarse + fine (models/sinnerf.py:32-42 SL1Loss,
@@ -204,6 +208,155 @@ rays_bwd_finish_kernel(const double* __restrict__ partials, int n_partials, floa
   }
 }
 
+// ---- the reference's other cameras: llff (get_ndc_rays, datasets/ray_utils.py:123-164) and dtu (get_ray_directions_dtu,
+// datasets/dtu_proj.py:17-35) -------------------------------------------------------------------------------------------
+struct Camera {
+  float fx, fy, cx, cy;
+  int convention;                  // 0: ((i-cx)/fx, -(j-cy)/fy, -1)  ray_utils.py:89-91;  1: ((i-cx)/fx, (j-cy)/fy, +1)  dtu_proj.py:31-33
+  int ndc;                         // 1: the rays go through the NDC map below
+  float ax, ay, ndc_near, two_near;// -1/(W/(2 focal)), -1/(H/(2 focal)), near, 2 near: the reference's Python floats, cast once
+};
+struct Window { int x0, y0, sx, sy, pw, ph; };
+
+SN_DEV void camera_dir(const Camera& cam, const Window& win, long idx, float& d0, float& d1, float& d2) {
+  const int iy = (int)(idx / win.pw), ix = (int)(idx - (long)iy * win.pw);
+  const float i = (float)(win.x0 + ix * win.sx), j = (float)(win.y0 + iy * win.sy);
+  d0 = __fdiv_rn(__fsub_rn(i, cam.cx), cam.fx);
+  const float v = __fdiv_rn(__fsub_rn(j, cam.cy), cam.fy);
+  d1 = cam.convention ? v : -v;
+  d2 = cam.convention ? 1.0f : -1.0f;
+}
+
+// rays_d = directions @ c2w[:, :3].T, left to right as generate_rays_kernel does                       ray_utils.py:109
+SN_DEV void rotate(const float* R, float d0, float d1, float d2, float* d) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    d[a] = __fadd_rn(__fadd_rn(__fmul_rn(d0, R[4 * a + 0]), __fmul_rn(d1, R[4 * a + 1])), __fmul_rn(d2, R[4 * a + 2]));
+}
+
+// get_ndc_rays op by op, one rounding per torch op (scalar / tensor is tensor.reciprocal() * scalar in torch)
+SN_DEV void ndc_map(const Camera& cam, float* o, float* d) {
+  const float t = __fdiv_rn(-__fadd_rn(cam.ndc_near, o[2]), d[2]);                                        // :145
+  const float px = __fadd_rn(o[0], __fmul_rn(t, d[0])), py = __fadd_rn(o[1], __fmul_rn(t, d[1])),         // :146
+              pz = __fadd_rn(o[2], __fmul_rn(t, d[2]));
+  const float ox_oz = __fdiv_rn(px, pz), oy_oz = __fdiv_rn(py, pz);                                       // :149-150
+  const float o2 = __fadd_rn(1.0f, __fmul_rn(__fdiv_rn(1.0f, pz), cam.two_near));                         // :155
+  const float u = __fdiv_rn(d[0], d[2]), v = __fdiv_rn(d[1], d[2]);
+  o[0] = __fmul_rn(cam.ax, ox_oz); o[1] = __fmul_rn(cam.ay, oy_oz); o[2] = o2;                            // :153-154
+  d[0] = __fmul_rn(cam.ax, __fsub_rn(u, ox_oz)); d[1] = __fmul_rn(cam.ay, __fsub_rn(v, oy_oz));           // :157-158
+  d[2] = __fsub_rn(1.0f, o2);                                                                             // :159
+}
+
+// The adjoint of ndc_map as autograd derives it from :145-159, fp32, forward intermediates recomputed.  pz is only approximately
+// -near: its derivative terms stay.  o, d: the map's INPUT; go, gd: in = gradient of the map's output, out = gradient of its input.
+SN_DEV void ndc_map_adjoint(const Camera& cam, const float* o, const float* d, float* go, float* gd) {
+  const float t = __fdiv_rn(-__fadd_rn(cam.ndc_near, o[2]), d[2]);
+  const float px = __fadd_rn(o[0], __fmul_rn(t, d[0])), py = __fadd_rn(o[1], __fmul_rn(t, d[1])),
+              pz = __fadd_rn(o[2], __fmul_rn(t, d[2]));
+  const float rz = __fdiv_rn(1.0f, pz), ox_oz = __fdiv_rn(px, pz), oy_oz = __fdiv_rn(py, pz);
+  const float u = __fdiv_rn(d[0], d[2]), v = __fdiv_rn(d[1], d[2]);
+  // d2 = 1 - o2, o2 = 1 + rz * two_near
+  const float g_rz = (go[2] - gd[2]) * cam.two_near;
+  // o0 = ax ox_oz, d0 = ax (u - ox_oz); o1, d1 alike
+  const float g_u = cam.ax * gd[0], g_v = cam.ay * gd[1];
+  const float g_a = cam.ax * go[0] - g_u, g_b = cam.ay * go[1] - g_v;
+  // ox_oz = px / pz, oy_oz = py / pz, rz = 1 / pz
+  const float g_px = g_a / pz, g_py = g_b / pz;
+  const float g_pz = (-g_rz * (rz * rz) - g_a * ox_oz / pz) - g_b * oy_oz / pz;
+  // u = dx / dz, v = dy / dz
+  float g_dx = g_u / d[2], g_dy = g_v / d[2], g_dz = -g_u * u / d[2] - g_v * v / d[2];
+  // p = o + t d
+  const float g_t = (g_px * d[0] + g_py * d[1]) + g_pz * d[2];
+  g_dx += t * g_px; g_dy += t * g_py; g_dz += t * g_pz;
+  // t = -(near + oz) / dz
+  g_dz -= g_t * t / d[2];
+  go[0] = g_px; go[1] = g_py; go[2] = g_pz - g_t / d[2];
+  gd[0] = g_dx; gd[1] = g_dy; gd[2] = g_dz;
+}
+
+// generate_rays_kernel for any of the cameras; (convention 0, fx = fy = focal, cx = W/2, cy = H/2, ndc 0) writes its bits
+__global__ void __launch_bounds__(256)
+generate_rays_cam_kernel(const float* __restrict__ c2w, Camera cam, float near, float far, Window win, float* __restrict__ rays) {
+  const long total = (long)win.pw * win.ph;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = c2w[k];
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    float d0, d1, d2, o[3] = {R[3], R[7], R[11]}, d[3];                                    // rays_o = c2w[:, 3]  ray_utils.py:114
+    camera_dir(cam, win, idx, d0, d1, d2);
+    rotate(R, d0, d1, d2, d);
+    if (cam.ndc) ndc_map(cam, o, d);
+    float4* out = reinterpret_cast<float4*>(rays + idx * 8);
+    out[0] = make_float4(o[0], o[1], o[2], d[0]); out[1] = make_float4(d[1], d[2], near, far);
+  }
+}
+
+// the NDC map over rays that exist already (n, 8); columns 6, 7 pass through.  One thread reads its whole ray before it writes
+// it: rays_out may be rays_in (no __restrict__)
+__global__ void __launch_bounds__(256)
+ndc_rays_kernel(const float* rays_in, long n, Camera cam, float* rays_out) {
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
+    const float4* in = reinterpret_cast<const float4*>(rays_in + idx * 8);
+    const float4 lo = in[0], hi = in[1];
+    float o[3] = {lo.x, lo.y, lo.z}, d[3] = {lo.w, hi.x, hi.y};
+    ndc_map(cam, o, d);
+    float4* out = reinterpret_cast<float4*>(rays_out + idx * 8);
+    out[0] = make_float4(o[0], o[1], o[2], d[0]); out[1] = make_float4(d[1], d[2], hi.z, hi.w);
+  }
+}
+
+__global__ void __launch_bounds__(256)
+ndc_rays_bwd_kernel(const float* __restrict__ rays_in, const float* __restrict__ g_out, long n, Camera cam, float* __restrict__ g_in) {
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
+    const float4* in = reinterpret_cast<const float4*>(rays_in + idx * 8);
+    const float4* g = reinterpret_cast<const float4*>(g_out + idx * 8);
+    const float4 lo = in[0], hi = in[1], glo = g[0], ghi = g[1];
+    const float o[3] = {lo.x, lo.y, lo.z}, d[3] = {lo.w, hi.x, hi.y};
+    float go[3] = {glo.x, glo.y, glo.z}, gd[3] = {glo.w, ghi.x, ghi.y};
+    ndc_map_adjoint(cam, o, d, go, gd);
+    float4* out = reinterpret_cast<float4*>(g_in + idx * 8);
+    out[0] = make_float4(go[0], go[1], go[2], gd[0]); out[1] = make_float4(gd[1], gd[2], 0.0f, 0.0f);
+  }
+}
+
+// rays_bwd_partials_kernel for any of the cameras: with ndc on, the upstream gradient of each ray first goes back through the
+// NDC map (the world ray is recomputed from c2w as generate_rays_cam_kernel computes it), in registers.  The sums, their order
+// and the finish kernel are those of rays_bwd_partials_kernel.
+__global__ void __launch_bounds__(256)
+rays_cam_bwd_partials_kernel(const float* __restrict__ g_rays, const float* __restrict__ c2w, Camera cam, Window win,
+                             double* __restrict__ partials) {
+  __shared__ double sh[4];
+  const long total = (long)win.pw * win.ph;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = cam.ndc ? c2w[k] : 0.0f;
+  double a[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    float c0, c1, c2;
+    camera_dir(cam, win, idx, c0, c1, c2);
+    const double d0 = (double)c0, d1 = (double)c1, d2 = (double)c2;
+    const float4* g = reinterpret_cast<const float4*>(g_rays + idx * 8);
+    const float4 lo = g[0], hi = g[1];
+    float gof[3] = {lo.x, lo.y, lo.z}, gdf[3] = {lo.w, hi.x, hi.y};
+    if (cam.ndc) {
+      const float o[3] = {R[3], R[7], R[11]};
+      float d[3];
+      rotate(R, c0, c1, c2, d);
+      ndc_map_adjoint(cam, o, d, gof, gdf);
+    }
+    const double go[3] = {(double)gof[0], (double)gof[1], (double)gof[2]}, gd[3] = {(double)gdf[0], (double)gdf[1], (double)gdf[2]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      a[4 * r + 0] += gd[r] * d0; a[4 * r + 1] += gd[r] * d1; a[4 * r + 2] += gd[r] * d2; a[4 * r + 3] += go[r];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+    const double v = block_sum(a[k], sh);
+    if (threadIdx.x == 0) partials[blockIdx.x * 12 + k] = v;
+  }
+}
+
 }  // namespace snx
 
 extern "C" int sn_generate_rays_launch(const float* c2w, int H, int W, float focal, float near, float far, int x0, int y0,
@@ -229,6 +382,57 @@ extern "C" int sn_generate_rays_backward_launch(const float* g_rays, int H, int 
   hipLaunchKernelGGL(rays_bwd_partials_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, H, W, focal, x0, y0, sx, sy,
                      pw, ph, partials);
   hipLaunchKernelGGL(rays_bwd_finish_kernel, dim3(1), dim3(256), 0, stream, partials, (int)blocks, g_c2w);
+  return (int)hipGetLastError();
+}
+
+static snx::Camera make_camera(float fx, float fy, float cx, float cy, int convention, int ndc, float ax, float ay, float ndc_near) {
+  return snx::Camera{fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near, (float)(2.0 * (double)ndc_near)};
+}
+
+extern "C" int sn_generate_rays_cam_launch(const float* c2w, float fx, float fy, float cx, float cy, int convention, int ndc, float ax,
+                                           float ay, float ndc_near, float near, float far, int x0, int y0, int sx, int sy, int pw,
+                                           int ph, float* rays, hipStream_t stream) {
+  const long total = (long)pw * ph;
+  if (total <= 0) return 0;
+  long blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(snx::generate_rays_cam_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, c2w,
+                     make_camera(fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near), near, far, snx::Window{x0, y0, sx, sy, pw, ph}, rays);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sn_generate_rays_cam_backward_launch(const float* g_rays, const float* c2w, float fx, float fy, float cx, float cy,
+                                                    int convention, int ndc, float ax, float ay, float ndc_near, int x0, int y0, int sx,
+                                                    int sy, int pw, int ph, void* workspace, float* g_c2w, hipStream_t stream) {
+  using namespace snx;
+  const long total = (long)pw * ph;
+  long blocks = (total + 255) / 256;
+  if (blocks < 1) blocks = 1;                    // an empty window still writes its 12 zeros
+  if (blocks > RAYS_BWD_BLOCKS) blocks = RAYS_BWD_BLOCKS;
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(rays_cam_bwd_partials_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, c2w,
+                     make_camera(fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near), Window{x0, y0, sx, sy, pw, ph}, partials);
+  hipLaunchKernelGGL(rays_bwd_finish_kernel, dim3(1), dim3(256), 0, stream, partials, (int)blocks, g_c2w);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sn_ndc_rays_launch(const float* rays_in, long n_rays, float ax, float ay, float ndc_near, float* rays_out,
+                                  hipStream_t stream) {
+  if (n_rays <= 0) return 0;
+  long blocks = (n_rays + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(snx::ndc_rays_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, n_rays,
+                     make_camera(1.0f, 1.0f, 0.0f, 0.0f, 0, 1, ax, ay, ndc_near), rays_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sn_ndc_rays_backward_launch(const float* rays_in, const float* g_rays_out, long n_rays, float ax, float ay,
+                                           float ndc_near, float* g_rays_in, hipStream_t stream) {
+  if (n_rays <= 0) return 0;
+  long blocks = (n_rays + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(snx::ndc_rays_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, g_rays_out, n_rays,
+                     make_camera(1.0f, 1.0f, 0.0f, 0.0f, 0, 1, ax, ay, ndc_near), g_rays_in);
   return (int)hipGetLastError();
 }
 

@@ -5,6 +5,11 @@ Reference: ``datasets/ray_utils.py:86-133`` (``get_ray_directions`` + ``get_rays
 ``blender_ray_patch_1image_rot3d.py:201-211``; strided patches ``:487-498``).  The reference builds the (H*W, 8) array on
 the CPU in the DataLoader and copies it to the device (``eval.py:155``); here ``sn_generate_rays`` writes it directly in
 HBM from the 12 floats of ``c2w``.
+
+The reference's other two cameras go through ``sn_generate_rays_cam``: llff, whose rays pass ``get_ndc_rays``
+(``datasets/ray_utils.py:123-164``; ``llff_ray_patch_1image_proj.py:473-483, :541-545, :676-682``), and dtu, with two focal
+lengths, a principal point and the OpenCV signs (``get_ray_directions_dtu``, ``datasets/dtu_proj.py:17-35``).  ``get_ndc_rays``
+is the reference's function of that name over rays that exist already (``sn_ndc_rays``).
 """
 import torch
 
@@ -42,19 +47,120 @@ class _GetRaysFn(torch.autograd.Function):
         return g_c2w, None, None, None, None, None, None
 
 
-def get_rays(H, W, focal, c2w, near, far, window=None):
+CONVENTIONS = {"opengl": 0, "opencv": 1}
+
+
+def _camera_args(H, W, cam):
+    """the arguments sn_generate_rays_cam and its backward share, between c2w and the window"""
+    fx, fy, cx, cy, convention, ndc_near = cam
+    ndc = ndc_near is not None
+    return (H, W, fx, fy, cx, cy, convention, int(ndc), fx, float(ndc_near) if ndc else 0.0)      # ndc_focal = fx (= fy with NDC)
+
+
+def _generate_cam(c2w, H, W, cam, near, far, win):
+    rays = torch.empty((win[4] * win[5], 8), dtype=torch.float32, device=c2w.device)
+    with torch.cuda.device(c2w.device):
+        _lib.check(_lib.lib.sn_generate_rays_cam(_lib.ptr(c2w), *_camera_args(H, W, cam), float(near), float(far), *win,
+                                                 _lib.ptr(rays), _lib.stream_ptr()), "sn_generate_rays_cam")
+    return rays
+
+
+class _GetRaysCamFn(torch.autograd.Function):
+    """``get_rays`` for the llff / dtu cameras under autograd: the direction stack (ray_utils.py:89-91 or dtu_proj.py:31-33),
+    ray_utils.py:109-114 and, with NDC, get_ndc_rays (:144-162) are ordinary differentiable torch ops in the reference."""
+
+    @staticmethod
+    def forward(ctx, c2w, H, W, cam, near, far, win):
+        ctx.args = (H, W, cam, win)
+        ctx.save_for_backward(c2w)
+        return _generate_cam(c2w, H, W, cam, near, far, win)
+
+    @staticmethod
+    def backward(ctx, g_rays):
+        H, W, cam, win = ctx.args
+        c2w, = ctx.saved_tensors
+        g_rays = g_rays.contiguous().float()
+        dev = g_rays.device
+        ws = torch.empty(int(_lib.lib.sn_generate_rays_backward_workspace_bytes()), dtype=torch.uint8, device=dev)
+        g_c2w = torch.empty((3, 4), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.sn_generate_rays_cam_backward(_lib.ptr(g_rays), _lib.ptr(c2w), *_camera_args(H, W, cam), *win,
+                                                              _lib.ptr(ws), _lib.ptr(g_c2w), _lib.stream_ptr()),
+                       "sn_generate_rays_cam_backward")
+        return g_c2w, None, None, None, None, None, None
+
+
+def get_rays(H, W, focal, c2w, near, far, window=None, *, center=None, convention="opengl", ndc_near=None):
     """(n, 8) fp32 rays ``[o(3), d(3), near, far]`` on ``c2w``'s device, row-major over pixels.
 
     ``c2w``: (3,4) camera-to-world tensor on the ROCm device.  ``window = (x0, y0, stride_x, stride_y, patch_w, patch_h)``
     selects a strided patch; default = the full frame.  When ``c2w.requires_grad`` (under grad mode) the result carries the
-    pose gradient (``sn_generate_rays_backward``): optimise ``c2w`` through ``render_rays``."""
+    pose gradient (``sn_generate_rays_backward`` / ``sn_generate_rays_cam_backward``): optimise ``c2w`` through ``render_rays``.
+
+    The camera: ``focal`` is one focal length or an ``(fx, fy)`` pair, ``center = (cx, cy)`` the principal point (default
+    ``(W/2, H/2)``), ``convention`` ``"opengl"`` (``((i-cx)/fx, -(j-cy)/fy, -1)``: blender, llff) or ``"opencv"``
+    (``((i-cx)/fx, (j-cy)/fy, +1)``: dtu, ``dtu_proj.py:17-35``).  ``ndc_near`` (llff: 1.0) sends every ray through the reference's
+    ``get_ndc_rays(H, W, focal, ndc_near, ...)``; ``near`` / ``far`` are then the NDC bounds the dataset packs (0, 1).  With the
+    keyword defaults and one focal length this is ``sn_generate_rays`` as before; anything else is ``sn_generate_rays_cam``."""
     if not c2w.is_cuda:
         raise RuntimeError("sinnerf_amd.ray_utils.get_rays: c2w must be a CUDA/ROCm tensor (no CPU fallback)")
+    if convention not in CONVENTIONS:
+        raise ValueError(f"convention must be one of {sorted(CONVENTIONS)}, got {convention!r}")
     pose_grad = torch.is_grad_enabled() and c2w.requires_grad
     c2w = c2w.contiguous().float()
     if tuple(c2w.shape) != (3, 4):
         raise RuntimeError(f"c2w must be (3, 4), got {tuple(c2w.shape)}")
     win = tuple(window) if window is not None else (0, 0, 1, 1, W, H)
+    pair = isinstance(focal, (tuple, list)) or getattr(focal, "ndim", 0) > 0
+    if not pair and center is None and convention == "opengl" and ndc_near is None:
+        if pose_grad:
+            return _GetRaysFn.apply(c2w, H, W, focal, near, far, win)
+        return _generate(c2w, H, W, focal, near, far, win)
+    fx, fy = (float(focal[0]), float(focal[1])) if pair else (float(focal), float(focal))
+    if ndc_near is not None and fx != fy:
+        raise ValueError("the NDC map has one focal length (get_ndc_rays(H, W, focal, ...)): fx must equal fy")
+    cx, cy = (W / 2, H / 2) if center is None else (float(center[0]), float(center[1]))
+    cam = (fx, fy, cx, cy, CONVENTIONS[convention], None if ndc_near is None else float(ndc_near))
     if pose_grad:
-        return _GetRaysFn.apply(c2w, H, W, focal, near, far, win)
-    return _generate(c2w, H, W, focal, near, far, win)
+        return _GetRaysCamFn.apply(c2w, H, W, cam, near, far, win)
+    return _generate_cam(c2w, H, W, cam, near, far, win)
+
+
+class _NdcRaysFn(torch.autograd.Function):
+    """get_ndc_rays on (n, 8) rays; backward = sn_ndc_rays_backward at the saved world rays"""
+
+    @staticmethod
+    def forward(ctx, rays, H, W, focal, near):
+        ctx.args = (H, W, focal, near)
+        ctx.save_for_backward(rays)
+        out = torch.empty_like(rays)
+        with torch.cuda.device(rays.device):
+            _lib.check(_lib.lib.sn_ndc_rays(_lib.ptr(rays), rays.shape[0], H, W, focal, near, _lib.ptr(out), _lib.stream_ptr()),
+                       "sn_ndc_rays")
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        H, W, focal, near = ctx.args
+        rays, = ctx.saved_tensors
+        g_out = g_out.contiguous().float()
+        g_in = torch.empty_like(rays)
+        with torch.cuda.device(rays.device):
+            _lib.check(_lib.lib.sn_ndc_rays_backward(_lib.ptr(rays), _lib.ptr(g_out), rays.shape[0], H, W, focal, near, _lib.ptr(g_in),
+                                                     _lib.stream_ptr()), "sn_ndc_rays_backward")
+        return g_in, None, None, None, None
+
+
+def get_ndc_rays(H, W, focal, near, rays_o, rays_d):
+    """The reference's ``get_ndc_rays`` (``datasets/ray_utils.py:123-164``) for callers that hold world-space rays already:
+    ``rays_o``, ``rays_d`` (N_rays, 3) on the ROCm device -> ``(rays_o, rays_d)`` in NDC, fp32.  ``near``: a float (the depth of the
+    near plane; llff: 1.0).  Differentiable in ``rays_o`` and ``rays_d`` (``sn_ndc_rays_backward``)."""
+    if not (rays_o.is_cuda and rays_d.is_cuda):
+        raise RuntimeError("sinnerf_amd.ray_utils.get_ndc_rays: rays_o and rays_d must be CUDA/ROCm tensors (no CPU fallback)")
+    if rays_o.shape != rays_d.shape or rays_o.shape[-1] != 3:
+        raise RuntimeError(f"rays_o and rays_d must both be (N_rays, 3), got {tuple(rays_o.shape)} and {tuple(rays_d.shape)}")
+    shape = rays_o.shape
+    o, d = rays_o.reshape(-1, 3).float(), rays_d.reshape(-1, 3).float()
+    rays = torch.cat([o, d, o.new_zeros((o.shape[0], 2))], 1)
+    out = _NdcRaysFn.apply(rays, int(H), int(W), float(focal), float(near))
+    return out[:, 0:3].reshape(shape), out[:, 3:6].reshape(shape)
