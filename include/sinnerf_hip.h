@@ -373,6 +373,36 @@ int sn_render_loss(const float* rgb_coarse, const float* rgb_fine, const float* 
                    float w_rgb, float w_depth, float* g_rgb_coarse, float* g_rgb_fine, float* g_depth_coarse,
                    float* g_depth_fine, void* workspace, float* out, void* stream);
 
+/* ---- losses on the rendered PATCHES, forward + gradients in two launches (additive within ABI 5): losses.py:94-109 L2_SSIM_Loss --
+ * nn.MSELoss 'mean' of coarse and of fine against the target, plus w_ssim x kornia 0.6.3 ssim_loss of fine against the target:
+ *   g[k] = exp(-(k - window/2)^2 / (2 1.5^2)) normalised to sum 1; F = per-channel correlation with g (x) g after reflect padding by
+ *   window/2 (the edge pixel is not repeated); mu1 = F(a), mu2 = F(b), s11 = F(a a) - mu1^2, s22 = F(b b) - mu2^2, s12 = F(a b) - mu1 mu2;
+ *   ssim = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2) + 1e-12), C1 = 0.01^2, C2 = 0.03^2;
+ *   ssim_loss = mean over B C H W of clamp((1 - ssim) / 2, 0, 1); the clamp passes gradient strictly inside (0, 1).
+ *   coarse, fine, target: DEVICE fp32 (B, H, W, C), CHANNEL-LAST -- the (B H W, C) rows of a render, or its (B H W) depths with C = 1.
+ *   coarse or fine may be NULL (its term is 0), not both; use_ssim needs fine.
+ *   use_ssim = 0: the MSE pair alone, any C (losses.py:12-22 on a patch); window is ignored.
+ *   out[4] = mse_coarse, mse_fine, ssim_loss, total = w_mse (mse_coarse + mse_fine) + w_ssim ssim_loss.
+ *   g_coarse, g_fine: gradients of `total`, channel-last (NULL = not wanted).  The target receives none.
+ *   workspace: the bytes the query returns for the same (B, H, W, C, use_ssim), DEVICE scratch.  Results are deterministic.
+ * SN_E_BADARG: a null required pointer; B, H, W or C <= 0; with use_ssim an even or non-positive window or C not in {1, 3}.
+ * SN_E_BADSHAPE: with use_ssim, H <= window/2 or W <= window/2.  SN_E_UNSUPPORTED: window > SN_PATCH_LOSS_MAX_WINDOW.
+ * SN_E_TOOLARGE: 2^31 elements or more.                                                                                      */
+#define SN_PATCH_LOSS_MAX_WINDOW 31
+long sn_patch_loss_workspace_bytes(int B, int H, int W, int C, int use_ssim);
+int sn_patch_loss(const float* coarse, const float* fine, const float* target, int B, int H, int W, int C, int use_ssim, int window,
+                  float w_mse, float w_ssim, float* g_coarse, float* g_fine, void* workspace, float* out, void* stream);
+
+/* ---- kornia inverse_depth_smoothness_loss(idepth, image) (models/sinnerf.py:370-373, 395-398), forward + gradients in two launches:
+ *   dx(t) = t[.., :, :-1] - t[.., :, 1:], dy alike along H; wx = exp(-mean_c |dx(image)|), wy alike;
+ *   out[0] = mean |dx(idepth) wx| + mean |dy(idepth) wy|.
+ *   idepth (B, H, W), image (B, H, W, C) channel-last: DEVICE fp32.  g_idepth, g_image: gradients of out[0] in the same layouts (NULL =
+ *   not wanted); |.| has derivative sign with sign(0) = 0.  workspace: the bytes the query returns.
+ * SN_E_BADARG: a null required pointer; B, H, W or C <= 0.  SN_E_BADSHAPE: H < 2 or W < 2.  SN_E_TOOLARGE: 2^31 elements or more.   */
+long sn_depth_smoothness_workspace_bytes(void);
+int sn_depth_smoothness(const float* idepth, const float* image, int B, int H, int W, int C, float* g_idepth, float* g_image,
+                        void* workspace, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,10 @@ SIGNATURES = {
     "sn_render_loss_workspace_bytes": (_long, []),
     "sn_render_loss": (_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_vp, _int, _long, _float, _float, c_fp, c_fp, c_fp, c_fp,
                               c_vp, c_fp, c_vp]),
+    "sn_patch_loss_workspace_bytes": (_long, [_int, _int, _int, _int, _int]),
+    "sn_patch_loss": (_int, [c_fp, c_fp, c_fp, _int, _int, _int, _int, _int, _int, _float, _float, c_fp, c_fp, c_vp, c_fp, c_vp]),
+    "sn_depth_smoothness_workspace_bytes": (_long, []),
+    "sn_depth_smoothness": (_int, [c_fp, c_fp, _int, _int, _int, _int, c_fp, c_fp, c_vp, c_fp, c_vp]),
     "sn_composite_backward": (_int, [c_fp, c_fp, c_fp, c_fp, _float, _long, _int, _int, c_fp, c_fp, c_fp, c_fp, c_vp]),
     "sn_ray_grads_workspace_bytes": (_long, [_long, _int]),
     "sn_ray_grads": (_int, [c_fp, c_fp, c_fp, _int, c_vp, _long, c_fp, c_fp, _long, _int, c_vp, c_fp, c_vp]),

@@ -351,6 +351,44 @@ int sn_render_loss(const float* rgb_coarse, const float* rgb_fine, const float* 
                                (hipStream_t)stream);
 }
 
+// ---- the losses on the rendered patches (sn_patch_loss.hip): every refusal below returns before a launch
+namespace {
+// B, H, W, C > 0 and fewer than 2^31 elements: grids, the int tile arithmetic and the workspace offsets stay in range
+int check_patch(int B, int H, int W, int C) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return SN_E_BADARG;
+  const __int128 n = (__int128)B * H * W * C;
+  return n >= ((__int128)1 << 31) ? SN_E_TOOLARGE : 0;
+}
+}  // namespace
+
+long sn_patch_loss_workspace_bytes(int B, int H, int W, int C, int use_ssim) {
+  if (const int refused = check_patch(B, H, W, C)) return refused;
+  return sn_patch_loss_workspace_bytes_impl(B, H, W, C, use_ssim ? 1 : 0);
+}
+
+int sn_patch_loss(const float* coarse, const float* fine, const float* target, int B, int H, int W, int C, int use_ssim, int window,
+                  float w_mse, float w_ssim, float* g_coarse, float* g_fine, void* workspace, float* out, void* stream) {
+  if (!target || !workspace || !out || (!coarse && !fine)) return SN_E_BADARG;
+  if (const int refused = check_patch(B, H, W, C)) return refused;
+  if (use_ssim) {
+    if (!fine || window <= 0 || window % 2 == 0 || (C != 1 && C != 3)) return SN_E_BADARG;
+    if (H <= window / 2 || W <= window / 2) return SN_E_BADSHAPE;                // reflect padding needs pad < size
+    if (window > SN_PATCH_LOSS_MAX_WINDOW) return SN_E_UNSUPPORTED;              // the tile with its halo must fit in LDS
+  }
+  return sn_patch_loss_launch(coarse, fine, target, B, H, W, C, use_ssim ? 1 : 0, window, w_mse, w_ssim, g_coarse, g_fine, workspace, out,
+                              (hipStream_t)stream);
+}
+
+long sn_depth_smoothness_workspace_bytes(void) { return sn_depth_smoothness_workspace_bytes_impl(); }
+
+int sn_depth_smoothness(const float* idepth, const float* image, int B, int H, int W, int C, float* g_idepth, float* g_image,
+                        void* workspace, float* out, void* stream) {
+  if (!idepth || !image || !workspace || !out) return SN_E_BADARG;
+  if (const int refused = check_patch(B, H, W, C)) return refused;
+  if (H < 2 || W < 2) return SN_E_BADSHAPE;
+  return sn_depth_smoothness_launch(idepth, image, B, H, W, C, g_idepth, g_image, workspace, out, (hipStream_t)stream);
+}
+
 int sn_dw_gemm(const void* tasks, int n_tasks, void* stream) {
   if (!tasks || n_tasks < 0) return SN_E_BADARG;
   return sn_dw_launch(tasks, n_tasks, (hipStream_t)stream);

@@ -157,4 +157,12 @@ long sn_ray_grads_workspace_bytes_impl(long n_rays, int n_samples);
 int sn_ray_grads_launch(const float* w1, const float* w5, const float* wdir, int layout, const void* g_acts, long slot_rows,
                         const float* rays, const float* z_vals, long n_rays, int n_samples, void* workspace, float* g_rays,
                         hipStream_t stream);
+// the losses on the rendered patches (sn_patch_loss.hip); *_blocks_impl: partial records the first kernel writes
+long sn_patch_loss_blocks_impl(int B, int H, int W, int C, int use_ssim);
+long sn_patch_loss_workspace_bytes_impl(int B, int H, int W, int C, int use_ssim);
+int sn_patch_loss_launch(const float* coarse, const float* fine, const float* target, int B, int H, int W, int C, int use_ssim, int window,
+                         float w_mse, float w_ssim, float* g_coarse, float* g_fine, void* workspace, float* out, hipStream_t stream);
+long sn_depth_smoothness_workspace_bytes_impl();
+int sn_depth_smoothness_launch(const float* idepth, const float* image, int B, int H, int W, int C, float* g_idepth, float* g_image,
+                               void* workspace, float* out, hipStream_t stream);
 }  // extern "C"

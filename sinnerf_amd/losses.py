@@ -7,6 +7,17 @@ gradients w.r.t. the rendered tensors in one go; csrc/sn_next.hip):
 * ``psnr``           metrics.py:14-15
 * ``render_loss``    the fused form the system uses: MSE coarse+fine + w_depth * (SL1 coarse + SL1 fine) + PSNR stats
 
+and the losses on the rendered PATCHES, by ``sn_patch_loss`` / ``sn_depth_smoothness`` (csrc/sn_patch_loss.hip):
+
+* ``L2_SSIM_Loss``   losses.py:94-109        ``forward(inputs, targets) -> {'tot', 'l2', 'ssim'}``
+* ``ssim_loss``      kornia 0.6.3 ``kornia.losses.ssim_loss(img1, img2, window_size)``, gradient to ``img1``
+* ``inverse_depth_smoothness_loss``  kornia 0.6.3, gradients to ``idepth`` and ``image``
+* ``loss_dict``      losses.py:152-153 without ``'l2_vgg'`` (pretrained VGG weights are not available offline)
+
+The patch losses take NCHW tensors as kornia's do.  The kernels read channel-last memory: an NCHW view that is a permute of a
+contiguous (B, H, W, C) buffer -- ``rearrange(rgb, '(b p q) c -> b c p q')`` of a render result -- is used in place, anything else is
+copied once.
+
 No CPU fallback: CUDA (ROCm) fp32 tensors only.
 """
 import torch
@@ -95,9 +106,12 @@ def render_loss(results, rgbs=None, depths=None, w_rgb=1.0, w_depth=1.0, mask=No
 
 
 class MSELoss(torch.nn.Module):
-    """losses.py:12-22."""
+    """losses.py:12-22; (B, C, H, W) patches too, as the reference's ``patch_loss`` feeds them (models/sinnerf.py:348, 367-368)."""
 
     def forward(self, inputs, targets):
+        if targets.dim() == 4:
+            loss, _ = _PatchLossFn.apply(inputs.get("rgb_coarse"), inputs.get("rgb_fine"), targets, 0, 0, 1.0, 0.0)
+            return {"tot": loss, "l2": loss}
         loss, _ = render_loss(inputs, rgbs=targets)
         return {"tot": loss, "l2": loss}
 
@@ -119,3 +133,131 @@ def psnr(image_pred, image_gt):
     with torch.no_grad():
         _, stats = render_loss({"rgb_fine": image_pred}, rgbs=image_gt)
     return stats["psnr_fine"]
+
+
+# ---- losses on the rendered patches (csrc/sn_patch_loss.hip) ------------------------------------------------------------------------
+SSIM_WEIGHT = 2.8333                                # losses.py:109 "ratio from MonoDepth"
+
+
+def _channel_last(t, name):
+    """(B, C, H, W) -> ((B, H, W, C) contiguous fp32 tensor, in_place): the memory under a permuted channel-last buffer as it is, one
+    copy of anything else"""
+    if t is None:
+        return None, True
+    if not t.is_cuda:
+        raise ValueError(f"{name}: CUDA tensor required (the HIP path has no CPU fallback)")
+    if t.dim() != 4:
+        raise ValueError(f"{name}: (B, C, H, W) expected, got {tuple(t.shape)}")
+    v = t.detach().permute(0, 2, 3, 1)
+    in_place = v.is_contiguous() and v.dtype == torch.float32
+    return (v if in_place else v.to(torch.float32).contiguous()), in_place
+
+
+def _nchw_grad(g, in_place):
+    """a channel-last gradient buffer in the caller's layout"""
+    g = g.permute(0, 3, 1, 2)
+    return g if in_place else g.contiguous()
+
+
+class _PatchLossFn(torch.autograd.Function):
+    """(coarse, fine, target) NCHW -> (total, out[4] = mse_coarse, mse_fine, ssim_loss, total); out carries no gradient"""
+
+    @staticmethod
+    def forward(ctx, coarse, fine, target, use_ssim, window, w_mse, w_ssim):
+        ctx.set_materialize_grads(False)
+        ref = fine if fine is not None else coarse
+        if ref is None:
+            raise ValueError("patch loss: neither 'rgb_coarse' nor 'rgb_fine'")
+        (c, c_in), (f, f_in), (t, _) = _channel_last(coarse, "coarse"), _channel_last(fine, "fine"), _channel_last(target, "target")
+        B, H, W, C = (f if f is not None else c).shape
+        for name, x in (("coarse", c), ("target", t)):
+            if x is not None and tuple(x.shape) != (B, H, W, C):
+                raise ValueError(f"patch loss: {name} {tuple(x.permute(0, 3, 1, 2).shape)} != {(B, C, H, W)}")
+        dev = ref.device
+        g_c = torch.empty_like(c) if (c is not None and coarse.requires_grad) else None
+        g_f = torch.empty_like(f) if (f is not None and fine.requires_grad) else None
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            nbytes = _lib.lib.sn_patch_loss_workspace_bytes(B, H, W, C, int(use_ssim))
+            if nbytes < 0:
+                _lib.check(nbytes, "sn_patch_loss_workspace_bytes")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(_lib.lib.sn_patch_loss(_lib.ptr(c), _lib.ptr(f), _lib.ptr(t), B, H, W, C, int(use_ssim), int(window),
+                                              float(w_mse), float(w_ssim), _lib.ptr(g_c), _lib.ptr(g_f), _lib.ptr(ws), _lib.ptr(out),
+                                              _lib.stream_ptr()), "sn_patch_loss")
+        ctx.save_for_backward(*[g for g in (g_c, g_f) if g is not None])
+        ctx.have, ctx.in_place = (g_c is not None, g_f is not None), (c_in, f_in)
+        ctx.mark_non_differentiable(out)
+        return out[3].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_out):
+        if g_total is None:
+            return (None,) * 7
+        saved = list(ctx.saved_tensors)
+        scaled = list(torch._foreach_mul(saved, g_total)) if saved else []
+        res = [_nchw_grad(scaled.pop(0), in_place) if have else None for have, in_place in zip(ctx.have, ctx.in_place)]
+        return (*res, None, None, None, None, None)
+
+
+class _DepthSmoothnessFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, idepth, image):
+        ctx.set_materialize_grads(False)
+        (d, d_in), (im, im_in) = _channel_last(idepth, "idepth"), _channel_last(image, "image")
+        B, H, W, C = im.shape
+        if tuple(d.shape) != (B, H, W, 1):
+            raise ValueError(f"inverse_depth_smoothness_loss: idepth {tuple(idepth.shape)} and image {tuple(image.shape)} must be "
+                             "(B, 1, H, W) and (B, C, H, W)")
+        dev = idepth.device
+        g_d = torch.empty_like(d) if idepth.requires_grad else None
+        g_i = torch.empty_like(im) if image.requires_grad else None
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws = torch.empty(_lib.lib.sn_depth_smoothness_workspace_bytes(), dtype=torch.uint8, device=dev)
+            _lib.check(_lib.lib.sn_depth_smoothness(_lib.ptr(d), _lib.ptr(im), B, H, W, C, _lib.ptr(g_d), _lib.ptr(g_i), _lib.ptr(ws),
+                                                    _lib.ptr(out), _lib.stream_ptr()), "sn_depth_smoothness")
+        ctx.save_for_backward(*[g for g in (g_d, g_i) if g is not None])
+        ctx.have, ctx.in_place = (g_d is not None, g_i is not None), (d_in, im_in)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g_total):
+        if g_total is None:
+            return None, None
+        saved = list(ctx.saved_tensors)
+        scaled = list(torch._foreach_mul(saved, g_total)) if saved else []
+        return tuple(_nchw_grad(scaled.pop(0), in_place) if have else None for have, in_place in zip(ctx.have, ctx.in_place))
+
+
+def ssim_loss(img1, img2, window_size):
+    """kornia 0.6.3 ``ssim_loss`` (``max_val`` 1, ``eps`` 1e-12, reduction 'mean'): (B, C, H, W) with C in {1, 3}; the gradient goes to
+    ``img1``"""
+    total, _ = _PatchLossFn.apply(None, img1, img2, 1, window_size, 0.0, 1.0)
+    return total
+
+
+def inverse_depth_smoothness_loss(idepth, image):
+    """kornia 0.6.3: ``idepth`` (B, 1, H, W), ``image`` (B, C, H, W); gradients go to both"""
+    return _DepthSmoothnessFn.apply(idepth, image)
+
+
+class L2_SSIM_Loss(torch.nn.Module):
+    """losses.py:94-109 on (B, C, H, W) patches, C in {1, 3}.  'tot' carries the gradient; 'l2' and 'ssim' are its two parts as values."""
+
+    def forward(self, inputs, targets):
+        if "rgb_fine" not in inputs:        # the reference fails here with an unbound local `ssim`
+            raise KeyError("L2_SSIM_Loss needs inputs['rgb_fine']: the SSIM term is taken on the fine render (losses.py:103-105)")
+        total, out = _PatchLossFn.apply(inputs.get("rgb_coarse"), inputs["rgb_fine"], targets, 1, 11, 1.0, SSIM_WEIGHT)
+        return {"tot": total, "l2": out[0] + out[1], "ssim": out[2]}
+
+
+class _LossDict(dict):
+    def __getitem__(self, key):
+        if key == "l2_vgg":
+            raise NotImplementedError("patch_loss 'l2_vgg' (losses.py:135-149) needs torchvision's pretrained VGG16 weights, which "
+                                      "cannot be downloaded here; use 'mse' or 'l2_ssim'")
+        return super().__getitem__(key)
+
+
+loss_dict = _LossDict({"mse": MSELoss, "l2_ssim": L2_SSIM_Loss})                     # losses.py:152-153

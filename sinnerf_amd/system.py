@@ -22,7 +22,7 @@ from torch import nn
 from .nerf import Embedding, NeRF
 from .optim import FlatAdam
 from .parallel import all_reduce_mean_grads, broadcast_parameters
-from .losses import psnr, render_loss      # noqa: F401  (psnr re-exported: metrics.py:14-15)
+from .losses import inverse_depth_smoothness_loss, loss_dict, psnr, render_loss      # noqa: F401  (psnr re-exported: metrics.py:14-15)
 from .rendering import render_rays
 
 DEFAULT_HPARAMS = dict(N_samples=64, N_importance=64, use_disp=False, perturb=1.0, noise_std=1.0, chunk=32 * 1024,
@@ -31,7 +31,10 @@ DEFAULT_HPARAMS = dict(N_samples=64, N_importance=64, use_disp=False, perturb=1.
                        # the adversarial term of the reference's second training stage (opt.py:98,107; README "Step 2": 0.01).  It only
                        # takes effect once a discriminator module is attached (attach_discriminator): the discriminator itself stays on
                        # stock PyTorch (north_star) and is not part of this package
-                       dis_weight=0.0, dloss="hinge", patch_hw=None)
+                       dis_weight=0.0, dloss="hinge", patch_hw=None,
+                       # the reference's losses on the rendered patches (opt.py --patch_loss / --depth_smooth_weight / --proj_weight /
+                       # --dataset_name; patch_losses below).  The defaults add no term
+                       patch_loss="mse", depth_smooth_weight=0.0, proj_weight=1.0, dataset_name=None)
 
 
 
@@ -92,9 +95,7 @@ class SinNeRFSystem(nn.Module):
 
     def _side_patch(self, results_side, batch):
         """``rearrange(results_side['rgb_fine'], '(b p q) c -> b c p q')`` of sinnerf.py:327-330 for b = 1"""
-        hw = tuple(batch["real_patch"].shape[-2:]) if "real_patch" in batch else self.hparams.patch_hw
-        if hw is None:
-            raise RuntimeError("the discriminator needs the patch shape: pass patch_hw=(psx, psy) or a batch with 'real_patch'")
+        hw = self._patch_hw(batch)
         rgb = results_side["rgb_fine"]
         return rgb.reshape(1, hw[0], hw[1], 3).permute(0, 3, 1, 2)
 
@@ -202,31 +203,90 @@ class SinNeRFSystem(nn.Module):
         total, _ = render_loss(results_side, tgt.reshape(-1, 3))
         return total
 
-    def _training_step_patches(self, batch):
+    def _patch_hw(self, batch):
+        hw = tuple(batch["real_patch"].shape[-2:]) if "real_patch" in batch else self.hparams.patch_hw
+        if hw is None:
+            raise RuntimeError("the patch losses need the patch shape: pass patch_hw=(psx, psy) or a batch with 'real_patch'")
+        return hw
+
+    def patch_losses(self, results, results_full, results_side, results_proj, batch):
+        """The loss of the patch step from its four renders (sinnerf.py:309-406, 492-509) -> (loss, log).
+
+        Always: MSE (+ ``depth_weight`` x SmoothL1 depth) on ``results``, the ``rgbs_full`` term on ``results_full``, SmoothL1 on
+        ``results_proj`` and ``side_loss``.  The reference's further patch terms appear when their batch key is present:
+
+        * ``patch_loss == 'l2_ssim'``: the ``rgbs_full`` term is ``L2_SSIM_Loss`` on the (1, 3, psx, psy) patch (sinnerf.py:348);
+        * ``'depth_gt'``: ``depth_weight`` x the depth-patch term (:354-369; ``dtu_proj``: SmoothL1 over ``depth_gt > 0``, otherwise
+          ``patch_loss`` on the depth maps) and, for a blender dataset, 2 x SmoothL1 over ``depth_gt == 0`` (:382-387);
+        * ``'warp_patch_depth'``: ``proj_weight * depth_weight`` x SmoothL1 of the side depths over its positive pixels (:399-406,
+          504-505), zero when there is none -- decided on the device, no host sync;
+        * ``depth_smooth_weight > 0``: the four ``inverse_depth_smoothness_loss`` terms (:370-373, 395-398, 509).
+        """
         hp = self.hparams
-        r8 = lambda k: batch[k].reshape(-1, 8)
-        results = self(r8("rays"))                                              # sinnerf.py:304
-        results_full = self(r8("rays_full"))                                    # :305
-        results_side = self(r8("rays_side"))                                    # :306
-        results_proj = self(r8("rays_proj"))                                    # :307
         wd = hp.depth_weight
         depth = batch.get("depth")
         loss, stats = render_loss(results, batch["rgbs"].reshape(-1, 3), depth.reshape(-1) if (depth is not None and wd > 0) else None,
                                   w_depth=wd)                                    # :316 loss_g + :317-318 depth terms
         log = {"train/loss_g": loss.detach()}
-        if "rgbs_full" in batch:                                                # :347 patch_loss(results_full, rgbs_full)
-            l_full, _ = render_loss(results_full, batch["rgbs_full"].reshape(-1, 3))
+        patch_loss = loss_dict[hp.patch_loss]()                                 # sinnerf.py:152 (raises for 'l2_vgg')
+        as_patch = lambda t, c: t.reshape(1, *self._patch_hw(batch), c).permute(0, 3, 1, 2)     # '(b p q) c -> b c p q', b = 1
+        if "rgbs_full" in batch:                                                # :348 patch_loss(results_full, rgbs_full)
+            if hp.patch_loss == "mse":
+                l_full, _ = render_loss(results_full, batch["rgbs_full"].reshape(-1, 3))
+            else:
+                l_full = patch_loss({k: as_patch(results_full[k], 3) for k in ("rgb_coarse", "rgb_fine") if k in results_full},
+                                    as_patch(batch["rgbs_full"], 3))["tot"]
             loss = loss + l_full
         if wd > 0 and "depth_proj" in batch:                                    # :309-311 SL1 on the projected rays
             l_proj, _ = render_loss(results_proj, None, batch["depth_proj"].reshape(-1), w_depth=wd)
             loss = loss + l_proj
             log["train/loss_depth_proj"] = l_proj.detach()
+        if wd > 0 and "depth_gt" in batch:                                      # :354-369 the depth of the full patch
+            depth_gt = batch["depth_gt"].reshape(-1)
+            depths_full = {k: results_full[k] for k in ("depth_coarse", "depth_fine") if k in results_full}
+            if hp.dataset_name == "dtu_proj":
+                l_dp, _ = render_loss(depths_full, None, depth_gt, w_depth=wd, useMask=True)
+            else:
+                l_dp = wd * patch_loss({k.replace("depth", "rgb"): as_patch(v, 1) for k, v in depths_full.items()},
+                                       as_patch(depth_gt, 1))["tot"]
+            loss = loss + l_dp
+            if hp.dataset_name is not None and "blender" in hp.dataset_name:    # :382-387 the background stays at depth 0
+                l_bg, _ = render_loss(depths_full, None, depth_gt, w_depth=2.0 * wd, mask=depth_gt == 0)
+                loss = loss + l_bg
+        if wd > 0 and "warp_patch_depth" in batch:                              # :399-406, 504-505 pseudo labels from warping
+            warp = batch["warp_patch_depth"].reshape(-1)
+            depths_side = {k: results_side[k] for k in ("depth_coarse", "depth_fine") if k in results_side}
+            l_sd, st = render_loss(depths_side, None, warp, w_depth=1.0, useMask=True)
+            # no positive pixel: the kernel's mean over nothing is NaN with all-zero gradients; the term is 0 (reference: a host-side `if`)
+            l_sd = torch.where(st["n_depth"] > 0, l_sd, torch.zeros_like(l_sd))
+            loss = loss + (hp.proj_weight * wd) * l_sd
+            log["train/loss_side_depth"] = l_sd.detach()
+        if hp.depth_smooth_weight > 0:                                          # :370-373, 395-398, 509
+            l_sm = None
+            for res in (results_full, results_side):
+                if "rgb_fine" not in res:
+                    raise RuntimeError("depth_smooth_weight > 0 pairs the depth maps with 'rgb_fine': N_importance must be > 0")
+                image = as_patch(res["rgb_fine"], 3)
+                for k in ("depth_fine", "depth_coarse"):
+                    term = inverse_depth_smoothness_loss(as_patch(res[k], 1), image)
+                    l_sm = term if l_sm is None else l_sm + term
+            loss = loss + hp.depth_smooth_weight * l_sm
+            log["train/loss_depth_smooth"] = l_sm.detach()
         l_side = self.side_loss(results_side, batch)
         if l_side is not None:
             loss = loss + l_side
         p = stats["psnr_fine"] if "rgb_fine" in results else stats["psnr_coarse"]
         log.update({"train/loss": loss.detach(), "train/psnr": p})
-        return {"loss": loss, "progress_bar": {"train_psnr": p}, "log": log}
+        return loss, log
+
+    def _training_step_patches(self, batch):
+        r8 = lambda k: batch[k].reshape(-1, 8)
+        results = self(r8("rays"))                                              # sinnerf.py:304
+        results_full = self(r8("rays_full"))                                    # :305
+        results_side = self(r8("rays_side"))                                    # :306
+        results_proj = self(r8("rays_proj"))                                    # :307
+        loss, log = self.patch_losses(results, results_full, results_side, results_proj, batch)
+        return {"loss": loss, "progress_bar": {"train_psnr": log["train/psnr"]}, "log": log}
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):
@@ -355,7 +415,8 @@ class SinNeRFSystem(nn.Module):
                self.optimizer.flat.data_ptr() if isinstance(self.optimizer, FlatAdam) else None,
                self._flat.flat.data_ptr() if self._flat is not None else None,
                hp.N_samples, hp.N_importance, hp.use_disp, hp.perturb, hp.noise_std, hp.chunk, hp.depth_weight,
-               hp.compute_dtype, self.white_back, self.training)
+               hp.compute_dtype, self.white_back, self.training, hp.patch_loss, hp.depth_smooth_weight, hp.proj_weight,
+               hp.dataset_name)
         cache = self.__dict__.setdefault("_step_graphs", {})
         hit = cache.get(key)
         if hit is None:
