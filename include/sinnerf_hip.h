@@ -7,7 +7,10 @@
  *
  * Conventions: every pointer is a DEVICE pointer unless the name ends in _host; tensors are dense row-major
  * fp32; `stream` is a hipStream_t passed as void* (NULL = default stream).  Functions only enqueue work: no
- * allocation, no synchronisation, no global state.  Return 0 on success, a negative SN_E_* code for argument
+ * allocation, no synchronisation, no global state (one exception: the fp32 inference launches of sn_mlp_forward /
+ * sn_mlp_forward_embedded draw their work units from a library-owned device word per stream, zeroed on the stream
+ * in front of every launch -- a memset node when captured; at most 2^31 - 1 units of 32 points, SN_E_TOOLARGE
+ * beyond).  Return 0 on success, a negative SN_E_* code for argument
  * errors, a positive value = hipError_t of a failed launch.
  */
 #ifndef SINNERF_HIP_H

@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <mutex>
+#include <unordered_map>
 #include "../../include/sinnerf_hip.h"
 #include "sn_device.h"
 
@@ -40,6 +42,25 @@ inline int cu_count() {
 inline unsigned persistent_grid(long tiles) {
   const int n_cu = cu_count();
   return (unsigned)(tiles < n_cu ? tiles : n_cu);
+}
+
+// Kernels that deal their work units dynamically (sn_mlp_fwd_f32g.hip) draw tickets from one word of a per-device array of UNIT_WORDS
+// words that the kernel's translation unit owns.  unit_word(stream) = the index of the stream's word on the current device: launches on
+// one stream run one after the other and share a word (each zeroes it on the stream first), two streams never share one.  The map only
+// grows (a destroyed stream's handle, when the runtime hands it out again, keeps its word); -1 once UNIT_WORDS streams have been seen.
+constexpr int UNIT_WORDS = 1024;
+inline int unit_word(hipStream_t stream) {
+  static std::mutex mu;
+  static std::unordered_map<hipStream_t, int> of[MAX_DEVICES];
+  const int dev = current_device();
+  if (dev < 0) return -1;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = of[dev].find(stream);
+  if (it != of[dev].end()) return it->second;
+  const int w = (int)of[dev].size();
+  if (w >= UNIT_WORDS) return -1;
+  of[dev].emplace(stream, w);
+  return w;
 }
 
 // SN_DTYPE_EMB_BF16 (emb stored as bf16 in K-slot order) is refused unless the arithmetic is SN_DTYPE_BF16_STATE and the generated

@@ -51,6 +51,30 @@ SN_DEV void embed_dir(float x, float y, float z, int h, float* de) {
   de[14] = 0.0f;
   de[15] = 0.0f;
 }
+// The same 2 x 16 values when all 32 points of the wave lie on ONE ray (the caller's wave-uniform test): they are constants of the ray, so
+// lane L < 12 computes the band pair p = L % 6 of lane half L / 6 -- ONE sincos_rev per lane instead of six, the same operations on the same
+// argument: the same bits -- and lanes 12 / 13 contribute the identity slots.  line = 32 floats of wave-private LDS ([half][K-slot]); every
+// lane reads its half back as four ds_read_b128.  (LDS executes one wave's instructions in order: no barrier.)
+constexpr int DIR_LINE_FLOATS = 32;
+SN_DEV void embed_dir_shared(float x, float y, float z, int lane, float* line, float* de) {
+  const int L = lane < 12 ? lane : 0;
+  const int hh = L >= 6 ? 1 : 0, p = L - 6 * hh, c = p >= 3 ? p - 3 : p;
+  const float v = c == 0 ? x : c == 1 ? y : z;
+  const float scale = (hh ? 4.0f : 1.0f) * (p >= 3 ? 2.0f : 1.0f);
+  float2 sc;
+  sincos_rev(to_revolutions(v), scale, sc.x, sc.y);
+  if (lane < 12) *reinterpret_cast<float2*>(line + 16 * hh + 2 * p) = sc;
+  else if (lane == 12) *reinterpret_cast<float4*>(line + 12) = make_float4(x, y, 0.0f, 0.0f);
+  else if (lane == 13) *reinterpret_cast<float4*>(line + 28) = make_float4(z, 0.0f, 0.0f, 0.0f);
+  __builtin_amdgcn_wave_barrier();
+  const float4* src = reinterpret_cast<const float4*>(line + 16 * (lane >> 5));
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float4 t = src[q];
+    de[4 * q] = t.x; de[4 * q + 1] = t.y; de[4 * q + 2] = t.z; de[4 * q + 3] = t.w;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
 
 
 // Training forward: the embedded inputs of a point go to emb[point][128] in the reference's column order (nerf.py:36-41).

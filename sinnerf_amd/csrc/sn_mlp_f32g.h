@@ -29,7 +29,8 @@ constexpr int EPI_STEPS = 24, EPI_STEPS_STORE = 30;
 #ifndef SN_F32G_WAIT_G
 #define SN_F32G_WAIT_G 6
 #endif
-constexpr int F32G_LDS_BYTES = TAIL_LDS_BYTES + EPI_LDS_BYTES;   // bias / head table + the epilogue staging of four waves
+// bias / head table + the epilogue staging of four waves + their lines of the per-ray direction embedding (sn_mlp_common.h)
+constexpr int F32G_LDS_BYTES = TAIL_LDS_BYTES + EPI_LDS_BYTES + 4 * DIR_LINE_FLOATS * 4;
 constexpr int F32G_LDS_BYTES_STORE = TAIL_LDS_BYTES + XPOSE_LDS_BYTES;   // ... training forward: the staging tiles of the activation stores
 
 typedef __amdgpu_buffer_rsrc_t rsrc_t;

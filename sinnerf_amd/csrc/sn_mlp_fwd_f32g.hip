@@ -19,13 +19,34 @@
 //       - it is deferred into the next slab's first groups ACROSS layer boundaries too (the next layer reads a tile's K-slots only
 //         in its groups 4 t ..), so no layer end drains the matrix pipe.
 //   * what VALU work is left sits where it cannot be avoided: the embeddings (exact range reduction), the sigma head's 256 FMAs,
-//     ShiftedSoftplus and the rgb head -- 2.6 k instructions per 128-point tile beside 9 280 MFMAs per wave.
-// The training forward (activation stores) is this kernel's STORE instantiation, compiled as a translation unit of its own (see the
+//     ShiftedSoftplus and the rgb head -- 2.6 k instructions per 128-point tile beside 9 280 MFMAs per wave.  What the result does not
+//     need is gone from the inference kernels: the ray index of a point is one integer multiplication per wave on the SCALAR unit plus a
+//     per-lane carry (sn_ray_index.h; it was a 64-bit VALU division, twice), and the direction embedding is computed once per wave --
+//     one sincos_rev per lane, handed round through a wave-private LDS line -- where the wave's 32 points lie on one ray
+//     (sn_mlp_common.h embed_dir_shared; rays that end inside the wave take the per-lane path).  Same operations on the same arguments:
+//     the same bits.
+//   * the inference kernels deal WORK UNITS OF 32 POINTS -- one wave's share, the waves never synchronise -- by tickets: a returning
+//     agent-scope add on one device word per stream in flight (snh::unit_word; zeroed on the stream before the launch), requested a whole
+//     unit (258 us) ahead of its use.  A static partition ends when the slowest CU ends: stamped, the XCDs differ by 1.5 % in rate and
+//     the average CU stood idle for the last 1.0 % of a fine-pass launch (profiles/f32g_exit_spread.txt); with tickets 0.07 %.
+// The training forward (static partition, per-lane ray index: unchanged) (activation stores) is this kernel's STORE instantiation, compiled as a translation unit of its own (see the
 // launcher below); the backward chain of the same generation is sn_mlp_bwd_f32g.hip.  sn_mlp_fwd.hip / sn_mlp_bwd.hip (LDS ring, same
 // epilogues, same bits) remain behind SN_FLAG_F32_LDS_RING / SN_DTYPE_COMPILER_SCHEDULED.
 #include "sn_mlp_f32g.h"
+#include "sn_ray_index.h"
+
+#ifdef SN_F32G_STAMP_EXIT
+#define SN_F32G_STAMP_PARAM , unsigned long* __restrict__ stamp
+#define SN_F32G_STAMP_ARG , sn_f32g_stamp_buffer
+#else
+#define SN_F32G_STAMP_PARAM
+#define SN_F32G_STAMP_ARG
+#endif
 
 namespace snk {
+
+// work-unit tickets of the inference kernels: one word per stream in flight (snh::unit_word), zeroed on the launch stream before the launch
+__device__ unsigned f32g_unit_words[snh::UNIT_WORDS];
 
 constexpr unsigned slab_byte_offset(int s) { return (unsigned)(snl::slab_elem_offset(s) * 4); }
 
@@ -36,7 +57,8 @@ constexpr unsigned slab_byte_offset(int s) { return (unsigned)(snl::slab_elem_of
 template <bool SIGMA_ONLY, int INPUT_MODE, bool STORE>
 __global__ void __launch_bounds__(256)
 mlp_fwd_f32g_kernel(const char* __restrict__ blob, const float* __restrict__ in0, const float* __restrict__ in1, long P, int S,
-                    float* __restrict__ out, float* __restrict__ acts, float* __restrict__ emb, long slot_rows) {
+                    float* __restrict__ out, float* __restrict__ acts, float* __restrict__ emb, long slot_rows,
+                    unsigned unit_word, unsigned long ray_m, unsigned ray_sh SN_F32G_STAMP_PARAM) {
   constexpr int FD = STORE ? FD_STORE : FD_INFER;
   constexpr int NSTEPS = STORE ? EPI_STEPS_STORE : EPI_STEPS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -48,7 +70,14 @@ mlp_fwd_f32g_kernel(const char* __restrict__ blob, const float* __restrict__ in0
   const int wave = tid >> 6;
   const int j = lane & 31;
   const int h = lane >> 5;
-  const long n_tiles = (P + 127) / 128;
+  // inference: the unit of work is a wave's 32 points, drawn from a device word (the waves never synchronise: no wave waits for a slower
+  // CU's share at the end of the launch); training forward: the static partition, a workgroup's four waves on one 128-point tile
+#ifdef SN_F32G_STATIC_UNITS                      // timing build: the static partition in the inference kernels too
+  constexpr bool DYN = false;
+#else
+  constexpr bool DYN = !STORE;
+#endif
+  const long n_units = STORE ? (P + 127) / 128 * 4 : (P + 31) / 32;
   constexpr int N_USED = SIGMA_ONLY ? snl::SLAB_FIN : snl::N_SLABS;
 
   {
@@ -63,8 +92,6 @@ mlp_fwd_f32g_kernel(const char* __restrict__ blob, const float* __restrict__ in0
   unsigned voff = lane * 16;
   asm volatile("" : "+v"(voff));
   f32x4 fr[FD];
-#pragma unroll
-  for (int g = 0; g < FD - 1; ++g) fr[g] = load_frag(rs, voff, g * 1024);      // slab 0, groups 0 .. FD-2
   f32x16 acc0 = load_bias(lds_bias, 0, h), acc1;
   // epilogue staging: where this lane's accumulator quad q goes.  Inference: a tile of its own (quad q of lane l at 1024 q + 16 l).
   // Training forward: the quad's place in the [point row][feature] staging tile of the activation stores (row j, floats 8 q + 4 h ..;
@@ -80,22 +107,59 @@ mlp_fwd_f32g_kernel(const char* __restrict__ blob, const float* __restrict__ in0
   unsigned vzero;
   asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
   asm volatile("" : "+v"(epi_a));
+  float* const dir_line = reinterpret_cast<float*>(smem + TAIL_LDS_BYTES + EPI_LDS_BYTES) + wave * DIR_LINE_FLOATS;   // inference only
 
-  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-  const long p_wave = (tile * 4 + __builtin_amdgcn_readfirstlane(wave)) * 32;
+#ifdef SN_F32G_STAMP_EXIT
+  const unsigned long t_enter = __builtin_amdgcn_s_memrealtime();
+  unsigned long units_done = 0;
+#endif
+  // The ticket of the wave's next unit: ONE returning agent-scope add, issued by lane 0 a whole unit (258 us) ahead of its use.  Hand-placed:
+  // the compiler waits for a returning atomic where it is requested (its atomic optimizer reads the result back at once).  vmcnt retires in
+  // issue order and at least FD - 1 fragment loads are issued behind every request, so vmcnt(FD - 1) at the top of a unit -- the depth the
+  // ring holds anyway -- covers it.
+  unsigned* const unit_ctr = f32g_unit_words + unit_word;
+  unsigned ticket = 0, vone = 1;
+  auto request_unit = [&]() __attribute__((always_inline)) {
+    // (s_nop: the SALU -> VMEM wait states of the address pair, which hipcc pads for its own instructions only)
+    if (lane == 0) asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "+v"(ticket) : "v"(vzero), "v"(vone), "s"(unit_ctr) : "memory");
+  };
+  if (DYN) request_unit();
+#pragma unroll
+  for (int g = 0; g < FD - 1; ++g) fr[g] = load_frag(rs, voff, g * 1024);      // slab 0, groups 0 .. FD-2
+  const unsigned n_units32 = (unsigned)n_units;  // (inference: the launcher refuses more than snr::MAX_POINTS)
+  for (long unit = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wave);; unit += (long)gridDim.x * 4) {
+  if (DYN) {
+    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ticket) : "n"(FD - 1) : "memory");
+    const unsigned u = (unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
+    if (u >= n_units32) break;
+    unit = (long)u;
+    request_unit();
+  } else if (unit >= n_units) break;
+#ifdef SN_F32G_STAMP_EXIT
+  ++units_done;
+#endif
+  const long p_wave = unit * 32;
   const long p_raw = p_wave + j;
-  const bool valid = p_raw < P;
-  const long p = valid ? p_raw : P - 1;
+  // the points past the end repeat the last one.  Inference: as a wave-uniform bound on the lane's index (no 64-bit per-lane arithmetic)
+  const int j_last = (unsigned)unit + 1u == n_units32 ? (int)((P - 1) & 31) : 31;
+  const bool valid = STORE ? p_raw < P : j <= j_last;
+  const int jc = j < j_last ? j : j_last;
+  const long p = STORE ? (valid ? p_raw : P - 1) : p_wave + jc;
+  // inference: ray of the point = the wave's first ray + this lane's carry (sn_ray_index.h), as the byte offset of its row in `rays`
+  const unsigned long ray_w = (!STORE && INPUT_MODE == 0) ? snr::wave_ray((unsigned long)p_wave, ray_m, ray_sh) : 0;
+  const unsigned rem_w = snr::wave_rem((unsigned long)p_wave, ray_w, S);
+  const char* const rays_w = reinterpret_cast<const char*>(in0) + ray_w * 32;
+  unsigned ray_off = 0;
+  if (!STORE && INPUT_MODE == 0) ray_off = snr::lane_carry(rem_w + (unsigned)jc, S) * 32u;
 
   float xe[32];
   if (INPUT_MODE == 0) {
 #ifdef SN_F32G_NO_RAY_LOADS
     const float ox = 0.1f, oy = 0.2f, oz = 0.3f, dx = 0.5f, dy = 0.4f, dz = -0.7f, zz = 2.0f + 1e-6f * (float)p;
 #else
-    const long ray = p / S;
-    const float* rp = in0 + ray * 8;
+    const float* rp = STORE ? in0 + (p / S) * 8 : reinterpret_cast<const float*>(rays_w + ray_off);
     const float ox = rp[0], oy = rp[1], oz = rp[2], dx = rp[3], dy = rp[4], dz = rp[5];
-    const float zz = in1[p];
+    const float zz = STORE ? in1[p] : *reinterpret_cast<const float*>(reinterpret_cast<const char*>(in1 + p_wave) + (unsigned)jc * 4u);
 #endif
     // xyz = o + d*z with separate roundings (torch: mul then add, rendering.py:284-285)
     const float x = __fadd_rn(ox, __fmul_rn(dx, zz));
@@ -254,7 +318,7 @@ mlp_fwd_f32g_kernel(const char* __restrict__ blob, const float* __restrict__ in0
 #pragma unroll
     for (int st = 0; st < EPI_STEPS; ++st) relu_prog(SN_C(1), SN_C(7), 7, st, acc1);
     const float sigma = sg + __shfl_xor(sg, 32, 64) + lds_aux[snl::AUX_HEADB];
-    if (valid && h == 0) out[p_raw] = sigma;
+    if (valid && h == 0) (out + p_wave)[j] = sigma;          // (wave-uniform base + the lane's 32-bit offset)
     continue;                                    // (acc0 already holds slab 0's bias: slab 63 requested it as its s_next)
   }
 
@@ -265,12 +329,14 @@ mlp_fwd_f32g_kernel(const char* __restrict__ blob, const float* __restrict__ in0
   // dir_encoding + ShiftedSoftplus (nerf.py:142-143): reads set 0 and the dir embedding (VGPRs)
   float de[16];
   if (INPUT_MODE == 0) {
-    const float* rp = in0 + (p / S) * 8;
+    const float* rp = STORE ? in0 + (p / S) * 8 : reinterpret_cast<const float*>(rays_w + ray_off);
 #ifdef SN_F32G_NO_VALU_BLOCKS
 #pragma unroll
     for (int e = 0; e < 16; ++e) de[e] = rp[3] + (float)e;
 #else
-    embed_dir(rp[3], rp[4], rp[5], h, de);
+    // inference, all 32 points on one ray (wave-uniform): the embedding is a per-ray constant -- one sincos_rev per lane instead of six
+    if (!STORE && rem_w + (unsigned)j_last < (unsigned)S) embed_dir_shared(rp[3], rp[4], rp[5], lane, dir_line, de);
+    else embed_dir(rp[3], rp[4], rp[5], h, de);
 #endif
   } else {
     const float* row = in0 + p * (long)S;
@@ -343,10 +409,21 @@ mlp_fwd_f32g_kernel(const char* __restrict__ blob, const float* __restrict__ in0
       o.y = rgb_activation(o3[1]);
       o.z = rgb_activation(o3[2]);
       o.w = sigma;                               // cat([rgb, sigma]) nerf.py:146
-      reinterpret_cast<float4*>(out)[p_raw] = o;
+      reinterpret_cast<float4*>(out + 4 * p_wave)[j] = o;
     }
   }
-  }  // persistent tile loop
+  }  // persistent unit loop
+#ifdef SN_F32G_STAMP_EXIT                        // timing build: when each wave ran out of work, where it ran, how many units it drew
+  if (lane == 0) {
+    unsigned xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    unsigned long* rec = stamp + ((long)blockIdx.x * 4 + wave) * 4;
+    rec[0] = t_enter;
+    rec[1] = __builtin_amdgcn_s_memrealtime();
+    rec[2] = xcc & 15u;
+    rec[3] = units_done;
+  }
+#endif
 #undef SN_C
 #undef SN_SLABG
 #undef SN_LAYERG
@@ -364,6 +441,27 @@ mlp_fwd_f32g_kernel(const char* __restrict__ blob, const float* __restrict__ in0
 #define SN_F32G_ENTRY sn_mlp_forward_f32g
 #endif
 #define SN_F32G_LAUNCH_NAME(base) SN_LAUNCH_NAME(base)        // (one more level: the argument is expanded before ## pastes it)
+#ifdef SN_F32G_STAMP_EXIT                       // timing build: four 64-bit words per wave (enter, exit in 100 MHz ticks, XCD, units drawn)
+static unsigned long* sn_f32g_stamp_buffer = nullptr;
+extern "C" void sn_f32g_set_stamp_buffer(unsigned long* device_words) { sn_f32g_stamp_buffer = device_words; }
+#endif
+#if !defined(SN_F32G_TU_STORE) && !defined(SN_F32G_AB_STORE) && !defined(SN_F32G_STATIC_UNITS)
+// the stream's ticket word, zeroed on the stream (capturable: a memset node in front of the kernel node)
+static int f32g_zeroed_unit_word(hipStream_t stream, unsigned* word) {
+  static unsigned* base[snh::MAX_DEVICES];     // (benign race: every thread writes the same value)
+  const int dev = snh::current_device(), w = snh::unit_word(stream);
+  if (dev < 0 || w < 0) return SN_E_UNSUPPORTED;
+  unsigned* b = __atomic_load_n(&base[dev], __ATOMIC_RELAXED);
+  if (b == nullptr) {
+    const hipError_t e = hipGetSymbolAddress(reinterpret_cast<void**>(&b), HIP_SYMBOL(snk::f32g_unit_words));
+    if (e != hipSuccess) return (int)e;
+    __atomic_store_n(&base[dev], b, __ATOMIC_RELAXED);
+  }
+  *word = (unsigned)w;
+  return (int)hipMemsetAsync(b + w, 0, sizeof(unsigned), stream);
+}
+#define SN_F32G_DYNAMIC_UNITS 1
+#endif
 extern "C" int SN_F32G_LAUNCH_NAME(SN_F32G_ENTRY)(const void* blob, const float* in0, const float* in1, long n_points, int s_or_ld,
                                              int sigma_only, int input_mode, float* out, float* acts, float* emb, long slot_rows,
                                              hipStream_t stream) {
@@ -375,11 +473,23 @@ extern "C" int SN_F32G_LAUNCH_NAME(SN_F32G_ENTRY)(const void* blob, const float*
   dim3 grid(snh::persistent_grid(tiles)), block(256);      // persistent: one workgroup per CU (~400 registers per lane: one wave per SIMD)
   const size_t lds = store ? F32G_LDS_BYTES_STORE : F32G_LDS_BYTES;
   const char* b = reinterpret_cast<const char*>(blob);
+  unsigned word = 0;
+  snr::RayDiv rd = {0, 0};
+  if (!store) {                                  // inference: 32-bit unit tickets, ray index by multiplication (sn_ray_index.h)
+    if (n_points > snr::MAX_POINTS) return SN_E_TOOLARGE;
+    if (input_mode == 0 && s_or_ld < 1) return SN_E_BADARG;
+    if (input_mode == 0) rd = snr::make_ray_div(s_or_ld);
+#ifdef SN_F32G_DYNAMIC_UNITS
+    const int e = f32g_zeroed_unit_word(stream, &word);
+    if (e != 0) return e;
+#endif
+  }
 #define SN_LAUNCH(SO, IM, ST)                                                                                       \
   do {                                                                                                              \
     auto kfn = mlp_fwd_f32g_kernel<SO, IM, ST>;                                                                     \
     SN_ENSURE_DYN_LDS(kfn, lds);                                                                                    \
-    hipLaunchKernelGGL(kfn, grid, block, lds, stream, b, in0, in1, n_points, s_or_ld, out, acts, emb, slot_rows);   \
+    hipLaunchKernelGGL(kfn, grid, block, lds, stream, b, in0, in1, n_points, s_or_ld, out, acts, emb, slot_rows,    \
+                       word, (unsigned long)rd.m, (unsigned)rd.sh SN_F32G_STAMP_ARG);                                 \
   } while (0)
 #if defined(SN_F32G_AB)                         // timing builds (tools/build_variant_f32g.sh): ONE instantiation: the frame render's, or
 #ifdef SN_F32G_AB_STORE                         // the training forward's with -DSN_F32G_AB_STORE (which replaces BOTH objects)

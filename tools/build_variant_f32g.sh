@@ -3,6 +3,9 @@
 # ABI; load it with SINNERF_HIP_LIB=...; only ONE instantiation is compiled: the frame render's, or -- with -DSN_F32G_AB_STORE -- the
 # training forward's, replacing that translation unit of the library).
 # usage: tools/build_variant_f32g.sh name [-DSN_F32G_FD=16 -DSN_F32G_NO_ATOMICS -DSN_F32G_AB_STORE ...]
+#   -DSN_F32G_STATIC_UNITS   the static partition of the point tiles (workgroup b: tiles b, b + grid, ..) instead of the unit tickets
+#   -DSN_F32G_STAMP_EXIT     every wave records s_memrealtime at entry and exit, its XCD and its unit count (right results; the library
+#                            exports sn_f32g_set_stamp_buffer; tools/f32g_exit_spread.py runs it and prints the spread table)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift

@@ -2,7 +2,8 @@
 """fp32 inference MLP launch, fine-pass shape of the bench (160 000 rays x 128 samples = 20.48 M points): the round-6 kernel
 (csrc/sn_mlp_fwd_f32g.hip: fragments straight from L2, VALU-free trunk, no barrier) against the LDS-ring kernel of rounds 1-5
 (csrc/sn_mlp_fwd.hip, SN_FLAG_F32_LDS_RING) -- time, fraction of the 157.3 TF fp32 MFMA peak, and BIT IDENTITY of the outputs
-(full + sigma-only + pre-embedded rows).  usage: f32_infer_ab.py [reps]     (run under rocprofv3 --pmc for cycles / MFMA-busy)"""
+(full + sigma-only + pre-embedded rows).  usage: f32_infer_ab.py [reps [samples ...]]     (run under rocprofv3 --pmc for cycles / MFMA-busy;
+samples per ray: 128 = the fine pass (default), 64 = the coarse pass of the bench)"""
 import os
 import sys
 
@@ -15,17 +16,21 @@ from sinnerf_amd import rendering, _lib                # noqa: E402
 
 RING = 4                                               # SN_FLAG_F32_LDS_RING
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+SAMPLES = [int(a) for a in sys.argv[2:]] or [128]
 FULL_ONLY = bool(os.environ.get("F32_AB_FULL_ONLY"))     # timing variants (tools/build_variant_f32g.sh) only carry the frame render's kernel
 dev = torch.device("cuda:0")
 rays = torch.from_numpy(O.lego_rays(400, 400, 0)).to(dev)
-torch.manual_seed(0)
-z = torch.sort(torch.rand((rays.shape[0], 128), device=dev) * 4 + 2, -1)[0].contiguous()
 m = sinnerf_amd.NeRF(use_new_activation=True, compute_dtype="fp32")
 m.load_state_dict({k: torch.from_numpy(v) for k, v in O.init_params(1, True).items()})
 m = m.to(dev).eval()
-pts = rays.shape[0] * 128
-outs = {}
-with torch.no_grad():
+
+
+def one_shape(n_samples):
+    torch.manual_seed(0)
+    z = torch.sort(torch.rand((rays.shape[0], n_samples), device=dev) * 4 + 2, -1)[0].contiguous()
+    pts = rays.shape[0] * n_samples
+    outs = {}
+    print("%d rays x %d samples" % (rays.shape[0], n_samples))
     for name, flags in (("f32g (round 6)", 0), ("LDS ring (rounds 1-5)", RING), ("f32g (round 6) again", 0)):
         for sigma_only in ((False,) if FULL_ONLY else (False, True)):
             for _ in range(1):
@@ -46,6 +51,11 @@ with torch.no_grad():
         same = torch.equal(outs[(0, so)], outs[(RING, so)])
         print("bit-identical outputs (%s): %s" % ("sigma-only" if so else "full", same))
         assert same
+
+
+with torch.no_grad():
+    for n_samples in SAMPLES:
+        one_shape(n_samples)
     if FULL_ONLY:
         sys.exit(0)
     # pre-embedded rows through NeRF.forward's entry (sn_mlp_forward_embedded)
