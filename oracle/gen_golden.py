@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate golden vectors from the UNMODIFIED reference (run in the build container only).
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [--grads | --rays | --loss | --pfm | --classic-heads | --trained | --port-check]
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [--grads | --rays | --loss | --pfm | --classic-heads | --trained | --port-check | --wide]
 
 Imports ``models.rendering`` / ``models.nerf`` straight from ``/root/reference`` (read-only mount,
 never present on the GPU box), executes them on CPU/fp32 with seeded synthetic inputs and stores
@@ -165,7 +165,7 @@ def main():
     print("done ->", OUT)
 
 
-if __name__ == "__main__" and not any(f in sys.argv for f in ("--grads", "--rays", "--loss", "--pfm", "--classic-heads", "--trained", "--port-check")):
+if __name__ == "__main__" and not any(f in sys.argv for f in ("--grads", "--rays", "--loss", "--pfm", "--classic-heads", "--trained", "--port-check", "--wide")):
     main()
 
 
@@ -437,3 +437,44 @@ def main_port_check():
 
 if __name__ == "__main__" and "--port-check" in sys.argv:
     main_port_check()
+
+
+def main_wide():
+    """More than 64 samples per ray (the per-ray kernels give each lane C = ceil(S / 64) consecutive samples): three renders of
+    rays from main()'s lego_s selection, and sample_pdf alone at 300 and 1000 bins with the special rows of sample_pdf.npz."""
+    os.makedirs(OUT, exist_ok=True)
+    lego = O.lego_rays(400, 400, seed=0)
+    sel = np.random.RandomState(7).choice(lego.shape[0], 192, replace=False)
+    lego_s = np.ascontiguousarray(lego[sel])
+    case_render("render_wide_s200_ni300", lego_s[:12], (0, 1), True, N_samples=200, perturb=1.0, noise_std=0.5,
+                N_importance=300, white_back=True)
+    case_render("render_wide_s512_ni512", lego_s[:8], (0, 1), True, N_samples=512, perturb=0, noise_std=0,
+                N_importance=512, white_back=True)
+    case_render("render_wide_s1023_ni1", lego_s[:6], (0, 1), True, N_samples=1023, perturb=1.0, noise_std=1.0,
+                N_importance=1, white_back=False)
+
+    r = np.random.RandomState(13)
+    out = {}
+    n = 24
+    for m, k in ((300, 257), (1000, 64)):
+        bins = np.sort(r.uniform(2, 6, (n, m + 1)).astype(np.float32), -1)
+        w = r.uniform(0, 1, (n, m)).astype(np.float32) ** 4
+        w[0] = 0.0                              # all-zero row -> uniform pdf
+        w[1, :m // 2] = 0.0                     # half-empty prefix
+        w[2] = 0.0; w[2, (2 * m) // 7] = 1.0    # delta
+        u = r.uniform(0, 1, (n, k)).astype(np.float32)
+        u[3, 0] = 0.0; u[3, 1] = 1.0 - 2 ** -24
+        det = ref_rendering.sample_pdf(torch.from_numpy(bins), torch.from_numpy(w), k, det=True).numpy()
+        _rand = torch.rand
+        torch.rand = lambda *a, **kk: torch.from_numpy(u.copy())
+        try:
+            rnd = ref_rendering.sample_pdf(torch.from_numpy(bins), torch.from_numpy(w), k, det=False).numpy()
+        finally:
+            torch.rand = _rand
+        out.update({f"m{m}_bins": bins, f"m{m}_weights": w, f"m{m}_u": u, f"m{m}_out_det": det, f"m{m}_out_rand": rnd})
+    np.savez_compressed(os.path.join(OUT, "sample_pdf_wide.npz"), **out)
+    print("sample_pdf_wide", {k_: v.shape for k_, v in out.items()})
+
+
+if __name__ == "__main__" and "--wide" in sys.argv:
+    main_wide()

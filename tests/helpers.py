@@ -55,7 +55,9 @@ def check_render(res, ref, rel=REL_TOL, opa=OPACITY_ABS_TOL, tag="", floor=ABS_F
 
 RENDER_CASES = ["render_lego_eval_teacher", "render_lego_eval_rawinit", "render_llff_eval_128",
                 "render_lego_train_teacher", "render_lego_testtime", "render_llff_disp_coarse_only",
-                "render_ragged_small"]
+                "render_ragged_small",
+                # more than 64 samples per ray: 4 / 8 / 16 elements per lane in the per-ray kernels (gen_golden.py --wide)
+                "render_wide_s200_ni300", "render_wide_s512_ni512", "render_wide_s1023_ni1"]
 
 
 def well_conditioned(bins, weights, u, margin=1e-6, eps=1e-5):
