@@ -406,6 +406,45 @@ long sn_depth_smoothness_workspace_bytes(void);
 int sn_depth_smoothness(const float* idepth, const float* image, int B, int H, int W, int C, float* g_idepth, float* g_image,
                         void* workspace, float* out, void* stream);
 
+/* ---- the forward warp of the reference view and its depth into the unseen view (additive within ABI 5): project_with_depth +
+ * forward_warp of datasets/blender_ray_patch_1image_rot3d.py:103-150 (called per training sample, :481-484),
+ * blender_ray_patch_1image_proj.py:93-138 (with depth_mask, :135-137), llff_ray_patch_1image_proj.py:117-166 (painter's loop :161-165)
+ * and warp_img_proj_numpy of dtu_proj.py:236-273 (loop :266-271), as one rule.  All pointers are DEVICE pointers.
+ *   ref_depth (H, W) fp32; data (H, W, C) fp32 CHANNEL-LAST, may be NULL (C is then ignored and out_new is not written).
+ *   ref_proj[16], src_proj[16]: fp64, row-major 4x4, the [K E[:3]; 0 0 0 1] matrices dtu_proj.py passes and the others imply.
+ *   In fp64 on the device: M = (src_proj ref_proj^-1)[:3, :] (Gauss-Jordan, once); for source pixel (x, y) of depth d
+ *   p = M (x d, y d, d, 1); depth_src = (float)p2; xs = p0 / (p2 + eps), ys = p1 / (p2 + eps)  (eps: 1e-9 at llff :136, 0 at dtu);
+ *   target tx = clamp(floor(xs), 0, W - 1), ty = clamp(floor(ys), 0, H - 1), clamped in floating point before the integer conversion,
+ *   so +-inf ends on a border.  A NaN xs or ys DROPS the source pixel: the reference casts NaN to int64, which is undefined
+ *   (rot3d :145 "be careful with nan").  Zero-depth source pixels take part as in the reference (they share one target).
+ *   mode 0: the LAST source pixel in raster order wins a target (NumPy's fancy-index assignment with duplicates: the blender files).
+ *   mode 1: the smallest depth_src (as fp32) wins, ties to the lowest raster index: the painter's loop of llff and dtu -- except
+ *   where a depth_src is exactly 0.0, which that loop reads as "empty" and overwrites.
+ *   The scatter always covers the whole frame.  The window (x0, y0, stride_x, stride_y, out_w, out_h), as in sn_generate_rays (full
+ *   frame = (0, 0, 1, 1, W, H)), selects what is written, row-major over (iy, ix); any output may be NULL:
+ *     out_new (out_h out_w, C) the winner's data row bit for bit, zeros where nothing landed;  new_depth (out_h out_w) its depth_src, 0
+ *     where nothing landed;  mask (out_h out_w) uint8, 1 where a pixel landed (depth_mask);  winner (out_h out_w) int32 source raster
+ *     index or -1.
+ *   workspace: the bytes the query returns for (H, W); it need not be initialised (the keys are cleared on the stream).  Results are
+ *   deterministic: the same bits on every call.
+ * SN_E_BADARG: a null required pointer; H, W, stride_x, stride_y, out_w or out_h <= 0; a window that leaves the frame; mode not in
+ * {0, 1}; data given with C <= 0.  SN_E_TOOLARGE: H W >= 2^31.                                                               */
+long sn_forward_warp_workspace_bytes(int H, int W);
+int sn_forward_warp(const float* ref_depth, const float* data, int H, int W, int C, const double* ref_proj, const double* src_proj,
+                    double eps, int mode, int x0, int y0, int stride_x, int stride_y, int out_w, int out_h, float* out_new,
+                    float* new_depth, unsigned char* mask, int* winner, void* workspace, void* stream);
+
+/* ---- np.random.choice(len(proj_depths_full), num) over rays_full[depth_mask] (blender_ray_patch_1image_proj.py:390-394, :472-478)
+ * without the boolean compaction: with N = the number of non-zero elements of mask (n) uint8, idx[j] (int32) = the raster index of
+ * the min(floor((double)u[j] N), N - 1)-th of them in raster order, for u (m) fp32 in [0, 1) (a u outside, or NaN, is clamped to the
+ * first / last); N = 0 gives idx = -1 everywhere.  n_landed (one int32, may be NULL) receives N.  All DEVICE pointers; m may be 0.
+ * Block sums, their scan, a search over blocks and a ballot walk inside one: integer sums without atomics, deterministic.
+ * workspace: the bytes the query returns for n.
+ * SN_E_BADARG: a null required pointer, n <= 0, m < 0.  SN_E_TOOLARGE: n or m >= 2^31.                                          */
+long sn_select_landed_workspace_bytes(long n);
+int sn_select_landed(const unsigned char* mask, long n, const float* u, long m, int* idx, int* n_landed, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,7 @@ ABI_VERSION = 5                     # == SN_ABI_VERSION of include/sinnerf_hip.h
 
 c_fp = ctypes.c_void_p      # device float*
 c_vp = ctypes.c_void_p
-_long, _int, _float = ctypes.c_long, ctypes.c_int, ctypes.c_float
+_long, _int, _float, _double = ctypes.c_long, ctypes.c_int, ctypes.c_float, ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/sinnerf_hip.h line by line
 SIGNATURES = {
@@ -67,6 +67,11 @@ SIGNATURES = {
     "sn_patch_loss": (_int, [c_fp, c_fp, c_fp, _int, _int, _int, _int, _int, _int, _float, _float, c_fp, c_fp, c_vp, c_fp, c_vp]),
     "sn_depth_smoothness_workspace_bytes": (_long, []),
     "sn_depth_smoothness": (_int, [c_fp, c_fp, _int, _int, _int, _int, c_fp, c_fp, c_vp, c_fp, c_vp]),
+    "sn_forward_warp_workspace_bytes": (_long, [_int, _int]),
+    "sn_forward_warp": (_int, [c_fp, c_fp, _int, _int, _int, c_vp, c_vp, _double, _int, _int, _int, _int, _int, _int, _int, c_fp, c_fp,
+                               c_vp, c_vp, c_vp, c_vp]),
+    "sn_select_landed_workspace_bytes": (_long, [_long]),
+    "sn_select_landed": (_int, [c_vp, _long, c_fp, _long, c_vp, c_vp, c_vp, c_vp]),
     "sn_composite_backward": (_int, [c_fp, c_fp, c_fp, c_fp, _float, _long, _int, _int, c_fp, c_fp, c_fp, c_fp, c_vp]),
     "sn_ray_grads_workspace_bytes": (_long, [_long, _int]),
     "sn_ray_grads": (_int, [c_fp, c_fp, c_fp, _int, c_vp, _long, c_fp, c_fp, _long, _int, c_vp, c_fp, c_vp]),

@@ -389,6 +389,42 @@ int sn_depth_smoothness(const float* idepth, const float* image, int B, int H, i
   return sn_depth_smoothness_launch(idepth, image, B, H, W, C, g_idepth, g_image, workspace, out, (hipStream_t)stream);
 }
 
+// ---- the unseen-view forward warp (sn_warp.hip): every refusal below returns before a launch
+namespace {
+int check_frame(int H, int W) {
+  if (H <= 0 || W <= 0) return SN_E_BADARG;
+  return (long)H * W >= (1l << 31) ? SN_E_TOOLARGE : 0;
+}
+}  // namespace
+
+long sn_forward_warp_workspace_bytes(int H, int W) {
+  if (const int refused = check_frame(H, W)) return refused;
+  return sn_forward_warp_workspace_bytes_impl(H, W);
+}
+
+int sn_forward_warp(const float* ref_depth, const float* data, int H, int W, int C, const double* ref_proj, const double* src_proj,
+                    double eps, int mode, int x0, int y0, int stride_x, int stride_y, int out_w, int out_h, float* out_new,
+                    float* new_depth, unsigned char* mask, int* winner, void* workspace, void* stream) {
+  if (!ref_depth || !ref_proj || !src_proj || !workspace) return SN_E_BADARG;
+  if (const int refused = check_frame(H, W)) return refused;
+  if (stride_x <= 0 || stride_y <= 0 || out_w <= 0 || out_h <= 0 || (mode != 0 && mode != 1) || (data && C <= 0)) return SN_E_BADARG;
+  if (x0 < 0 || y0 < 0 || x0 + (long)(out_w - 1) * stride_x >= W || y0 + (long)(out_h - 1) * stride_y >= H) return SN_E_BADARG;
+  return sn_forward_warp_launch(ref_depth, data, H, W, C, ref_proj, src_proj, eps, mode, x0, y0, stride_x, stride_y, out_w, out_h,
+                                out_new, new_depth, mask, winner, workspace, (hipStream_t)stream);
+}
+
+long sn_select_landed_workspace_bytes(long n) {
+  if (n <= 0) return SN_E_BADARG;
+  if (n >= (1l << 31)) return SN_E_TOOLARGE;
+  return sn_select_landed_workspace_bytes_impl(n);
+}
+
+int sn_select_landed(const unsigned char* mask, long n, const float* u, long m, int* idx, int* n_landed, void* workspace, void* stream) {
+  if (!mask || !workspace || n <= 0 || m < 0 || (m > 0 && (!u || !idx))) return SN_E_BADARG;
+  if (n >= (1l << 31) || m >= (1l << 31)) return SN_E_TOOLARGE;
+  return sn_select_landed_launch(mask, n, u, m, idx, n_landed, workspace, (hipStream_t)stream);
+}
+
 int sn_dw_gemm(const void* tasks, int n_tasks, void* stream) {
   if (!tasks || n_tasks < 0) return SN_E_BADARG;
   return sn_dw_launch(tasks, n_tasks, (hipStream_t)stream);

@@ -186,4 +186,12 @@ int sn_patch_loss_launch(const float* coarse, const float* fine, const float* ta
 long sn_depth_smoothness_workspace_bytes_impl();
 int sn_depth_smoothness_launch(const float* idepth, const float* image, int B, int H, int W, int C, float* g_idepth, float* g_image,
                                void* workspace, float* out, hipStream_t stream);
+// the unseen-view forward warp and the draw among the landed pixels (sn_warp.hip)
+long sn_forward_warp_workspace_bytes_impl(int H, int W);
+int sn_forward_warp_launch(const float* ref_depth, const float* data, int H, int W, int C, const double* ref_proj, const double* src_proj,
+                           double eps, int mode, int x0, int y0, int stride_x, int stride_y, int out_w, int out_h, float* out_new,
+                           float* new_depth, unsigned char* mask, int* winner, void* workspace, hipStream_t stream);
+long sn_select_landed_workspace_bytes_impl(long n);
+int sn_select_landed_launch(const unsigned char* mask, long n, const float* u, long m, int* idx, int* n_landed, void* workspace,
+                            hipStream_t stream);
 }  // extern "C"
