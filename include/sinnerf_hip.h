@@ -26,7 +26,10 @@ extern "C" {
                             * 5: SN_DTYPE_F16 (inference entries, packer), SN_FLAG_F32_LDS_RING
                             *    (additive within 5: the pose-gradient entries sn_ray_grads, sn_ray_grads_workspace_bytes,
                             *    sn_composite_backward_rays, sn_generate_rays_backward and its workspace query; the camera entries
-                            *    sn_generate_rays_cam, sn_generate_rays_cam_backward, sn_ndc_rays, sn_ndc_rays_backward) */
+                            *    sn_generate_rays_cam, sn_generate_rays_cam_backward, sn_ndc_rays, sn_ndc_rays_backward
+                            *    and, with the intrinsics in device memory and their gradients, sn_generate_rays_cam_dev,
+                            *    sn_generate_rays_cam_dev_backward, sn_camera_backward_workspace_bytes, sn_ndc_rays_dev,
+                            *    sn_ndc_rays_dev_backward) */
 
 #define SN_DTYPE_F32 0  /* v_mfma_f32_32x32x2_f32, exact fp32                                          */
 #define SN_DTYPE_BF16 1 /* v_mfma_f32_32x32x16_bf16, bf16 operands / fp32 accumulate                    */
@@ -354,6 +357,39 @@ int sn_ndc_rays(const float* rays_in, long n_rays, int H, int W, float focal, fl
  * g_rays_in must not overlap the inputs.                                                                                     */
 int sn_ndc_rays_backward(const float* rays_in, const float* g_rays_out, long n_rays, int H, int W, float focal, float ndc_near,
                          float* g_rays_in, void* stream);
+
+/* ---- the camera entries with the INTRINSICS IN DEVICE MEMORY and their gradients (additive within ABI 5): a focal length that is
+ * being learnt lives in a device tensor; these entries never read it back, so they neither synchronise nor break a stream capture.
+ * intr: 4 floats (DEVICE) fx, fy, cx, cy;  with ndc = 1 the NDC map's focal length is intr[0] (ndc_focal = fx above).  The kernels are
+ * those of the entries above with the camera filled in on the device; -1/(W/(2 focal)), -1/(H/(2 focal)) are formed there in fp64
+ * with one cast, as on the host: for equal fp32 values sn_generate_rays_cam_dev writes the bits of sn_generate_rays_cam and
+ * sn_ndc_rays_dev those of sn_ndc_rays (in place allowed).  Pointers, H, W, the window, convention and ndc are refused on the host as
+ * above.  The VALUES of the intrinsics are NOT checked (that would need a sync): a focal length that is zero, negative or not finite
+ * gives what IEEE arithmetic gives -- inf / NaN rays and gradients, as the reference's torch ops would -- and no fault.           */
+int sn_generate_rays_cam_dev(const float* c2w, const float* intr, int H, int W, int convention, int ndc, float ndc_near, float near,
+                             float far, int x0, int y0, int stride_x, int stride_y, int patch_w, int patch_h, float* rays,
+                             void* stream);
+
+/* ---- backward of sn_generate_rays_cam_dev with respect to c2w AND the intrinsics.  g_c2w (12 floats) or g_intr (4 floats: dL/dfx,
+ * dL/dfy, dL/dcx, dL/dcy) may be NULL and is then not written; both NULL: SN_E_BADARG.  c2w is always read.  Per ray, with c the
+ * camera direction, gd the gradient of the world direction (after the NDC adjoint with ndc = 1), gc = c2w[:, :3]^T gd and s = -1 / +1
+ * for convention 0 / 1:   g_fx += gc0 (-c0 / fx),  g_cx += gc0 (-1 / fx),  g_fy += gc1 (-c1 / fy),  g_cy += gc1 (-s / fy);
+ * with ndc = 1, from the gradient (go', gd') of the map's output and its quotients:  g_ax += go'0 ox_oz + gd'0 (u - ox_oz),
+ * g_ay += go'1 oy_oz + gd'1 (v - oy_oz),  and g_intr[0] += g_ax (-2 / W) + g_ay (-2 / H).  Per-ray terms from the fp32 quantities of the
+ * forward, products and sums in fp64, per-block partials added in index order: deterministic, no atomics.  g_c2w has the bits of
+ * sn_generate_rays_cam_backward.  An empty window writes zeros.  workspace: sn_camera_backward_workspace_bytes bytes (DEVICE).      */
+long sn_camera_backward_workspace_bytes(void);
+int sn_generate_rays_cam_dev_backward(const float* g_rays, const float* c2w, const float* intr, int H, int W, int convention, int ndc,
+                                      float ndc_near, int x0, int y0, int stride_x, int stride_y, int patch_w, int patch_h,
+                                      void* workspace, float* g_c2w, float* g_intr, void* stream);
+
+/* ---- sn_ndc_rays / sn_ndc_rays_backward with the focal length in DEVICE memory (focal: 1 float).  The backward writes g_rays_in with
+ * the bits of sn_ndc_rays_backward and g_focal (1 float) = g_ax (-2 / W) + g_ay (-2 / H) from the sums above (zero for n_rays = 0);
+ * workspace: sn_camera_backward_workspace_bytes bytes.  The value of focal is not checked, as above.                             */
+int sn_ndc_rays_dev(const float* rays_in, long n_rays, int H, int W, const float* focal, float ndc_near, float* rays_out,
+                    void* stream);
+int sn_ndc_rays_dev_backward(const float* rays_in, const float* g_rays_out, long n_rays, int H, int W, const float* focal,
+                             float ndc_near, void* workspace, float* g_rays_in, float* g_focal, void* stream);
 
 /* ---- utils/__init__.py:19-21 (torch.optim.Adam, eps=1e-8) over one flat fp32 buffer (the all-reduce buffer).
  * step = 1-based iteration count (bias correction).                                                             */

@@ -84,6 +84,13 @@ SIGNATURES = {
                                              _int, _int, _int, _int, _int, _int, c_vp, c_fp, c_vp]),
     "sn_ndc_rays": (_int, [c_fp, _long, _int, _int, _float, _float, c_fp, c_vp]),
     "sn_ndc_rays_backward": (_int, [c_fp, c_fp, _long, _int, _int, _float, _float, c_fp, c_vp]),
+    "sn_generate_rays_cam_dev": (_int, [c_fp, c_fp, _int, _int, _int, _int, _float, _float, _float, _int, _int, _int, _int, _int, _int,
+                                        c_fp, c_vp]),
+    "sn_camera_backward_workspace_bytes": (_long, []),
+    "sn_generate_rays_cam_dev_backward": (_int, [c_fp, c_fp, c_fp, _int, _int, _int, _int, _float, _int, _int, _int, _int, _int, _int,
+                                                 c_vp, c_fp, c_fp, c_vp]),
+    "sn_ndc_rays_dev": (_int, [c_fp, _long, _int, _int, c_fp, _float, c_fp, c_vp]),
+    "sn_ndc_rays_dev_backward": (_int, [c_fp, c_fp, _long, _int, _int, c_fp, _float, c_vp, c_fp, c_fp, c_vp]),
     "sn_mlp_forward_embedded": (_int, [c_vp, _int, c_fp, _long, _int, _int, _int, c_fp, c_vp]),
     "sn_composite_forward": (_int, [c_fp, _int, c_fp, c_fp, c_fp, _float, _long, _int, _int, c_fp, c_fp, c_fp, c_vp]),
     "sn_sample_pdf": (_int, [c_fp, c_fp, c_fp, _long, _int, _int, c_fp, c_fp, c_vp]),

@@ -527,7 +527,7 @@ int sn_generate_rays_cam(const float* c2w, int H, int W, float fx, float fy, flo
   if (const int refused = check_camera(H, W, fx, fy, convention, ndc, ndc_focal, x0, y0, stride_x, stride_y, patch_w, patch_h))
     return refused;
   return sn_generate_rays_cam_launch(c2w, fx, fy, cx, cy, convention, ndc, ndc_scale(W, ndc_focal), ndc_scale(H, ndc_focal), ndc_near,
-                                     near, far, x0, y0, stride_x, stride_y, patch_w, patch_h, rays, (hipStream_t)stream);
+                                     near, far, x0, y0, stride_x, stride_y, patch_w, patch_h, rays, nullptr, H, W, (hipStream_t)stream);
 }
 
 int sn_generate_rays_cam_backward(const float* g_rays, const float* c2w, int H, int W, float fx, float fy, float cx, float cy,
@@ -539,18 +539,57 @@ int sn_generate_rays_cam_backward(const float* g_rays, const float* c2w, int H, 
   if (ndc && !c2w) return SN_E_BADARG;            // the NDC adjoint is taken at the world ray, which comes from c2w
   return sn_generate_rays_cam_backward_launch(g_rays, c2w, fx, fy, cx, cy, convention, ndc, ndc_scale(W, ndc_focal),
                                               ndc_scale(H, ndc_focal), ndc_near, x0, y0, stride_x, stride_y, patch_w, patch_h, workspace,
-                                              g_c2w, (hipStream_t)stream);
+                                              g_c2w, nullptr, H, W, nullptr, (hipStream_t)stream);
 }
 
 int sn_ndc_rays(const float* rays_in, long n_rays, int H, int W, float focal, float ndc_near, float* rays_out, void* stream) {
   if (!rays_in || !rays_out || n_rays < 0 || H < 1 || W < 1 || !positive_finite(focal)) return SN_E_BADARG;
-  return sn_ndc_rays_launch(rays_in, n_rays, ndc_scale(W, focal), ndc_scale(H, focal), ndc_near, rays_out, (hipStream_t)stream);
+  return sn_ndc_rays_launch(rays_in, n_rays, ndc_scale(W, focal), ndc_scale(H, focal), ndc_near, rays_out, nullptr, H, W,
+                            (hipStream_t)stream);
 }
 
 int sn_ndc_rays_backward(const float* rays_in, const float* g_rays_out, long n_rays, int H, int W, float focal, float ndc_near,
                          float* g_rays_in, void* stream) {
   if (!rays_in || !g_rays_out || !g_rays_in || n_rays < 0 || H < 1 || W < 1 || !positive_finite(focal)) return SN_E_BADARG;
   return sn_ndc_rays_backward_launch(rays_in, g_rays_out, n_rays, ndc_scale(W, focal), ndc_scale(H, focal), ndc_near, g_rays_in,
+                                     nullptr, H, W, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// ---- the same with the intrinsics in DEVICE memory: their values are not looked at on the host (that would be a sync); everything
+// else is checked as above (check_camera with focal lengths that pass)
+int sn_generate_rays_cam_dev(const float* c2w, const float* intr, int H, int W, int convention, int ndc, float ndc_near, float near,
+                             float far, int x0, int y0, int stride_x, int stride_y, int patch_w, int patch_h, float* rays,
+                             void* stream) {
+  if (!c2w || !intr || !rays) return SN_E_BADARG;
+  if (const int refused = check_camera(H, W, 1.0f, 1.0f, convention, ndc, 1.0f, x0, y0, stride_x, stride_y, patch_w, patch_h))
+    return refused;
+  return sn_generate_rays_cam_launch(c2w, 1.0f, 1.0f, 0.0f, 0.0f, convention, ndc, 0.0f, 0.0f, ndc_near, near, far, x0, y0, stride_x,
+                                     stride_y, patch_w, patch_h, rays, intr, H, W, (hipStream_t)stream);
+}
+
+long sn_camera_backward_workspace_bytes(void) { return sn_camera_backward_workspace_bytes_impl(); }
+
+int sn_generate_rays_cam_dev_backward(const float* g_rays, const float* c2w, const float* intr, int H, int W, int convention, int ndc,
+                                      float ndc_near, int x0, int y0, int stride_x, int stride_y, int patch_w, int patch_h,
+                                      void* workspace, float* g_c2w, float* g_intr, void* stream) {
+  if (!g_rays || !c2w || !intr || !workspace || (!g_c2w && !g_intr)) return SN_E_BADARG;
+  if (const int refused = check_camera(H, W, 1.0f, 1.0f, convention, ndc, 1.0f, x0, y0, stride_x, stride_y, patch_w, patch_h))
+    return refused;
+  return sn_generate_rays_cam_backward_launch(g_rays, c2w, 1.0f, 1.0f, 0.0f, 0.0f, convention, ndc, 0.0f, 0.0f, ndc_near, x0, y0,
+                                              stride_x, stride_y, patch_w, patch_h, workspace, g_c2w, intr, H, W, g_intr,
+                                              (hipStream_t)stream);
+}
+
+int sn_ndc_rays_dev(const float* rays_in, long n_rays, int H, int W, const float* focal, float ndc_near, float* rays_out,
+                    void* stream) {
+  if (!rays_in || !rays_out || !focal || n_rays < 0 || H < 1 || W < 1) return SN_E_BADARG;
+  return sn_ndc_rays_launch(rays_in, n_rays, 0.0f, 0.0f, ndc_near, rays_out, focal, H, W, (hipStream_t)stream);
+}
+
+int sn_ndc_rays_dev_backward(const float* rays_in, const float* g_rays_out, long n_rays, int H, int W, const float* focal,
+                             float ndc_near, void* workspace, float* g_rays_in, float* g_focal, void* stream) {
+  if (!rays_in || !g_rays_out || !focal || !workspace || !g_rays_in || !g_focal || n_rays < 0 || H < 1 || W < 1) return SN_E_BADARG;
+  return sn_ndc_rays_backward_launch(rays_in, g_rays_out, n_rays, 0.0f, 0.0f, ndc_near, g_rays_in, focal, H, W, workspace, g_focal,
                                      (hipStream_t)stream);
 }
 

@@ -158,15 +158,21 @@ int sn_generate_rays_backward_launch(const float* g_rays, int H, int W, float fo
                                      int ph, void* workspace, float* g_c2w, hipStream_t stream);
 // ... the same for any of the reference's cameras (fx, fy, cx, cy, sign convention) with the optional NDC stage, and the NDC map on
 // its own; a_x = -1/(W/(2 focal)), a_y = -1/(H/(2 focal)) arrive computed in double (sn_api.hip)
+// intr / focal != NULL: the intrinsics are read from DEVICE memory (fx, fy, cx, cy; one focal length for the NDC map alone), the
+// floats given for them are ignored and a_x, a_y are formed on the device from H, W; the backwards then write g_intr / g_focal too
 int sn_generate_rays_cam_launch(const float* c2w, float fx, float fy, float cx, float cy, int convention, int ndc, float ax, float ay,
                                 float ndc_near, float near, float far, int x0, int y0, int sx, int sy, int pw, int ph, float* rays,
-                                hipStream_t stream);
+                                const float* intr, int H, int W, hipStream_t stream);
+long sn_camera_backward_workspace_bytes_impl();
 int sn_generate_rays_cam_backward_launch(const float* g_rays, const float* c2w, float fx, float fy, float cx, float cy, int convention,
                                          int ndc, float ax, float ay, float ndc_near, int x0, int y0, int sx, int sy, int pw, int ph,
-                                         void* workspace, float* g_c2w, hipStream_t stream);
-int sn_ndc_rays_launch(const float* rays_in, long n_rays, float ax, float ay, float ndc_near, float* rays_out, hipStream_t stream);
+                                         void* workspace, float* g_c2w, const float* intr, int H, int W, float* g_intr,
+                                         hipStream_t stream);
+int sn_ndc_rays_launch(const float* rays_in, long n_rays, float ax, float ay, float ndc_near, float* rays_out, const float* focal, int H,
+                       int W, hipStream_t stream);
 int sn_ndc_rays_backward_launch(const float* rays_in, const float* g_rays_out, long n_rays, float ax, float ay, float ndc_near,
-                                float* g_rays_in, hipStream_t stream);
+                                float* g_rays_in, const float* focal, int H, int W, void* workspace, float* g_focal,
+                                hipStream_t stream);
 int sn_adam_step_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                         float wd, int step, hipStream_t stream);
 long sn_render_loss_workspace_bytes_impl();

@@ -10,6 +10,8 @@
 //                          the two above for the reference's other cameras: separate fx, fy, a principal point and the OpenCV
 //                          signs of dtu (datasets/dtu_proj.py:17-35), and the NDC map of llff (datasets/ray_utils.py:123-164)
 //                          with its adjoint, fused into ray generation / the pose sums or over an existing (n, 8) ray array.
+//                          As templates: <true> reads the intrinsics from DEVICE memory (a learnable focal length: no host
+//                          read) and the backwards add the sums of dL/d(fx, fy, cx, cy); <false> is the host-float code as before.
 //   loss_partials_kernel / loss_finish_kernel
 //                          the losses computed on the rendered rays right after the path: MSE coarse + fine
 //                          (losses.py:12-22, nn.MSELoss mean), SmoothL1 depth coarse + fine (models/sinnerf.py:32-42 SL1Loss,
@@ -218,6 +220,16 @@ struct Camera {
 };
 struct Window { int x0, y0, sx, sy, pw, ph; };
 
+// The intrinsics held in DEVICE memory (a learnable focal length: no host read, no sync).  a_x, a_y as ndc_scale forms them on the
+// host (sn_api.hip): in fp64 with one cast; __ddiv_rn so that no flag can change them.  2.0 * focal is exact.
+SN_DEV float ndc_scale_dev(int size, float focal) { return (float)__ddiv_rn(-1.0, __ddiv_rn((double)size, 2.0 * (double)focal)); }
+SN_DEV void camera_ndc_focal(Camera& cam, float focal, int H, int W) { cam.ax = ndc_scale_dev(W, focal); cam.ay = ndc_scale_dev(H, focal); }
+// intr = (fx, fy, cx, cy); the NDC map's focal length is fx
+SN_DEV void camera_intrinsics(Camera& cam, const float* intr, int H, int W) {
+  cam.fx = intr[0]; cam.fy = intr[1]; cam.cx = intr[2]; cam.cy = intr[3];
+  camera_ndc_focal(cam, intr[0], H, W);
+}
+
 SN_DEV void camera_dir(const Camera& cam, const Window& win, long idx, float& d0, float& d1, float& d2) {
   const int iy = (int)(idx / win.pw), ix = (int)(idx - (long)iy * win.pw);
   const float i = (float)(win.x0 + ix * win.sx), j = (float)(win.y0 + iy * win.sy);
@@ -234,16 +246,24 @@ SN_DEV void rotate(const float* R, float d0, float d1, float d2, float* d) {
     d[a] = __fadd_rn(__fadd_rn(__fmul_rn(d0, R[4 * a + 0]), __fmul_rn(d1, R[4 * a + 1])), __fmul_rn(d2, R[4 * a + 2]));
 }
 
+// the quotients of get_ndc_rays that a_x, a_y scale, one rounding per torch op
+struct NdcRatios { float pz, ox_oz, oy_oz, u, v; };
+SN_DEV NdcRatios ndc_ratios(const Camera& cam, const float* o, const float* d) {
+  NdcRatios q;
+  const float t = __fdiv_rn(-__fadd_rn(cam.ndc_near, o[2]), d[2]);                                        // :145
+  const float px = __fadd_rn(o[0], __fmul_rn(t, d[0])), py = __fadd_rn(o[1], __fmul_rn(t, d[1]));         // :146
+  q.pz = __fadd_rn(o[2], __fmul_rn(t, d[2]));
+  q.ox_oz = __fdiv_rn(px, q.pz); q.oy_oz = __fdiv_rn(py, q.pz);                                           // :149-150
+  q.u = __fdiv_rn(d[0], d[2]); q.v = __fdiv_rn(d[1], d[2]);
+  return q;
+}
+
 // get_ndc_rays op by op, one rounding per torch op (scalar / tensor is tensor.reciprocal() * scalar in torch)
 SN_DEV void ndc_map(const Camera& cam, float* o, float* d) {
-  const float t = __fdiv_rn(-__fadd_rn(cam.ndc_near, o[2]), d[2]);                                        // :145
-  const float px = __fadd_rn(o[0], __fmul_rn(t, d[0])), py = __fadd_rn(o[1], __fmul_rn(t, d[1])),         // :146
-              pz = __fadd_rn(o[2], __fmul_rn(t, d[2]));
-  const float ox_oz = __fdiv_rn(px, pz), oy_oz = __fdiv_rn(py, pz);                                       // :149-150
-  const float o2 = __fadd_rn(1.0f, __fmul_rn(__fdiv_rn(1.0f, pz), cam.two_near));                         // :155
-  const float u = __fdiv_rn(d[0], d[2]), v = __fdiv_rn(d[1], d[2]);
-  o[0] = __fmul_rn(cam.ax, ox_oz); o[1] = __fmul_rn(cam.ay, oy_oz); o[2] = o2;                            // :153-154
-  d[0] = __fmul_rn(cam.ax, __fsub_rn(u, ox_oz)); d[1] = __fmul_rn(cam.ay, __fsub_rn(v, oy_oz));           // :157-158
+  const NdcRatios q = ndc_ratios(cam, o, d);
+  const float o2 = __fadd_rn(1.0f, __fmul_rn(__fdiv_rn(1.0f, q.pz), cam.two_near));                       // :155
+  o[0] = __fmul_rn(cam.ax, q.ox_oz); o[1] = __fmul_rn(cam.ay, q.oy_oz); o[2] = o2;                        // :153-154
+  d[0] = __fmul_rn(cam.ax, __fsub_rn(q.u, q.ox_oz)); d[1] = __fmul_rn(cam.ay, __fsub_rn(q.v, q.oy_oz));   // :157-158
   d[2] = __fsub_rn(1.0f, o2);                                                                             // :159
 }
 
@@ -274,10 +294,14 @@ SN_DEV void ndc_map_adjoint(const Camera& cam, const float* o, const float* d, f
   gd[0] = g_dx; gd[1] = g_dy; gd[2] = g_dz;
 }
 
-// generate_rays_kernel for any of the cameras; (convention 0, fx = fy = focal, cx = W/2, cy = H/2, ndc 0) writes its bits
+// generate_rays_kernel for any of the cameras; (convention 0, fx = fy = focal, cx = W/2, cy = H/2, ndc 0) writes its bits.
+// DEV: the four intrinsics and a_x, a_y come from intr (DEVICE) instead of cam; everything after that is the same code.
+template <bool DEV>
 __global__ void __launch_bounds__(256)
-generate_rays_cam_kernel(const float* __restrict__ c2w, Camera cam, float near, float far, Window win, float* __restrict__ rays) {
+generate_rays_cam_kernel(const float* __restrict__ c2w, Camera cam, const float* __restrict__ intr, int H, int W, float near, float far,
+                         Window win, float* __restrict__ rays) {
   const long total = (long)win.pw * win.ph;
+  if (DEV) camera_intrinsics(cam, intr, H, W);
   float R[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) R[k] = c2w[k];
@@ -293,8 +317,10 @@ generate_rays_cam_kernel(const float* __restrict__ c2w, Camera cam, float near, 
 
 // the NDC map over rays that exist already (n, 8); columns 6, 7 pass through.  One thread reads its whole ray before it writes
 // it: rays_out may be rays_in (no __restrict__)
+template <bool DEV>
 __global__ void __launch_bounds__(256)
-ndc_rays_kernel(const float* rays_in, long n, Camera cam, float* rays_out) {
+ndc_rays_kernel(const float* rays_in, long n, Camera cam, const float* __restrict__ focal, int H, int W, float* rays_out) {
+  if (DEV) camera_ndc_focal(cam, focal[0], H, W);
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
     const float4* in = reinterpret_cast<const float4*>(rays_in + idx * 8);
     const float4 lo = in[0], hi = in[1];
@@ -305,32 +331,66 @@ ndc_rays_kernel(const float* rays_in, long n, Camera cam, float* rays_out) {
   }
 }
 
+// The sums behind dL/d(fx, fy, cx, cy), next to the 12 pose sums; a_x = -2 focal / W and a_y = -2 focal / H are summed on their own
+// and folded into the focal length by the finish kernel.
+constexpr int CAM_SUMS = 18;       // 12 pose sums, g_fx, g_fy, g_cx, g_cy, g_ax, g_ay
+constexpr int NDC_SUMS = 2;        // g_ax, g_ay: the NDC map on its own
+
+// d(a_x ox_oz, a_y oy_oz, ., a_x (u - ox_oz), a_y (v - oy_oz), .) / d(a_x, a_y) against the gradient (go, gd) of the map's OUTPUT,
+// from the fp32 quantities the forward computes; products and sums in fp64
+SN_DEV void ndc_scale_sums(const Camera& cam, const float* o, const float* d, const float* go, const float* gd, double& g_ax, double& g_ay) {
+  const NdcRatios q = ndc_ratios(cam, o, d);
+  g_ax += (double)go[0] * (double)q.ox_oz + (double)gd[0] * (double)__fsub_rn(q.u, q.ox_oz);
+  g_ay += (double)go[1] * (double)q.oy_oz + (double)gd[1] * (double)__fsub_rn(q.v, q.oy_oz);
+}
+
+// FOCAL: the focal length comes from DEVICE memory and its gradient is wanted: per-block partials of g_ax, g_ay (NDC_SUMS) as well
+template <bool FOCAL>
 __global__ void __launch_bounds__(256)
-ndc_rays_bwd_kernel(const float* __restrict__ rays_in, const float* __restrict__ g_out, long n, Camera cam, float* __restrict__ g_in) {
+ndc_rays_bwd_kernel(const float* __restrict__ rays_in, const float* __restrict__ g_out, long n, Camera cam,
+                    const float* __restrict__ focal, int H, int W, float* __restrict__ g_in, double* __restrict__ partials) {
+  __shared__ double sh[4];
+  if (FOCAL) camera_ndc_focal(cam, focal[0], H, W);
+  double g_ax = 0.0, g_ay = 0.0;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
     const float4* in = reinterpret_cast<const float4*>(rays_in + idx * 8);
     const float4* g = reinterpret_cast<const float4*>(g_out + idx * 8);
     const float4 lo = in[0], hi = in[1], glo = g[0], ghi = g[1];
     const float o[3] = {lo.x, lo.y, lo.z}, d[3] = {lo.w, hi.x, hi.y};
     float go[3] = {glo.x, glo.y, glo.z}, gd[3] = {glo.w, ghi.x, ghi.y};
+    if (FOCAL) ndc_scale_sums(cam, o, d, go, gd, g_ax, g_ay);
     ndc_map_adjoint(cam, o, d, go, gd);
     float4* out = reinterpret_cast<float4*>(g_in + idx * 8);
     out[0] = make_float4(go[0], go[1], go[2], gd[0]); out[1] = make_float4(gd[1], gd[2], 0.0f, 0.0f);
+  }
+  if (FOCAL) {
+    const double vx = block_sum(g_ax, sh), vy = block_sum(g_ay, sh);
+    if (threadIdx.x == 0) { partials[blockIdx.x * NDC_SUMS + 0] = vx; partials[blockIdx.x * NDC_SUMS + 1] = vy; }
   }
 }
 
 // rays_bwd_partials_kernel for any of the cameras: with ndc on, the upstream gradient of each ray first goes back through the
 // NDC map (the world ray is recomputed from c2w as generate_rays_cam_kernel computes it), in registers.  The sums, their order
 // and the finish kernel are those of rays_bwd_partials_kernel.
+// INTR: the intrinsics come from intr (DEVICE) and their sums follow the 12 (CAM_SUMS per block): with c the camera direction,
+// gc = R^T gd the gradient of it and s the sign of the convention,  c0 = (i - cx) / fx,  c1 = s (j - cy) / fy  give
+//   g_fx += gc0 (-c0 / fx)   g_cx += gc0 (-1 / fx)   g_fy += gc1 (-c1 / fy)   g_cy += gc1 (-s / fy)
+// c2w is then always read.  The first 12 sums are the same expressions over the same rays in the same order either way.
+template <bool INTR>
 __global__ void __launch_bounds__(256)
-rays_cam_bwd_partials_kernel(const float* __restrict__ g_rays, const float* __restrict__ c2w, Camera cam, Window win,
-                             double* __restrict__ partials) {
+rays_cam_bwd_partials_kernel(const float* __restrict__ g_rays, const float* __restrict__ c2w, Camera cam,
+                             const float* __restrict__ intr, int H, int W, Window win, double* __restrict__ partials) {
+  constexpr int NS = INTR ? CAM_SUMS : 12;
   __shared__ double sh[4];
   const long total = (long)win.pw * win.ph;
+  if (INTR) camera_intrinsics(cam, intr, H, W);
   float R[12];
 #pragma unroll
-  for (int k = 0; k < 12; ++k) R[k] = cam.ndc ? c2w[k] : 0.0f;
-  double a[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < 12; ++k) R[k] = (INTR || cam.ndc) ? c2w[k] : 0.0f;
+  double a[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) a[k] = 0.0;
+  const double fx = (double)cam.fx, fy = (double)cam.fy, s = cam.convention ? 1.0 : -1.0;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     float c0, c1, c2;
     camera_dir(cam, win, idx, c0, c1, c2);
@@ -342,6 +402,7 @@ rays_cam_bwd_partials_kernel(const float* __restrict__ g_rays, const float* __re
       const float o[3] = {R[3], R[7], R[11]};
       float d[3];
       rotate(R, c0, c1, c2, d);
+      if constexpr (INTR) ndc_scale_sums(cam, o, d, gof, gdf, a[NS - 2], a[NS - 1]);
       ndc_map_adjoint(cam, o, d, gof, gdf);
     }
     const double go[3] = {(double)gof[0], (double)gof[1], (double)gof[2]}, gd[3] = {(double)gdf[0], (double)gdf[1], (double)gdf[2]};
@@ -349,11 +410,45 @@ rays_cam_bwd_partials_kernel(const float* __restrict__ g_rays, const float* __re
     for (int r = 0; r < 3; ++r) {
       a[4 * r + 0] += gd[r] * d0; a[4 * r + 1] += gd[r] * d1; a[4 * r + 2] += gd[r] * d2; a[4 * r + 3] += go[r];
     }
+    if constexpr (INTR) {
+      const double gc0 = (gd[0] * (double)R[0] + gd[1] * (double)R[4]) + gd[2] * (double)R[8];
+      const double gc1 = (gd[0] * (double)R[1] + gd[1] * (double)R[5]) + gd[2] * (double)R[9];
+      a[12] += gc0 * (-d0 / fx); a[13] += gc1 * (-d1 / fy); a[14] += gc0 * (-1.0 / fx); a[15] += gc1 * (-s / fy);
+    }
   }
 #pragma unroll
-  for (int k = 0; k < 12; ++k) {
+  for (int k = 0; k < NS; ++k) {
     const double v = block_sum(a[k], sh);
-    if (threadIdx.x == 0) partials[blockIdx.x * 12 + k] = v;
+    if (threadIdx.x == 0) partials[blockIdx.x * NS + k] = v;
+  }
+}
+
+// rays_bwd_finish_kernel for NS sums per block: the <= RAYS_BWD_BLOCKS partials added in index order, then
+//   CAM_SUMS: g_c2w (12) and g_intr = (g_fx + g_ax sx + g_ay sy, g_fy, g_cx, g_cy);   NDC_SUMS: g_intr[0] = g_ax sx + g_ay sy,
+// sx = da_x / dfocal = -2 / W, sy = -2 / H.  An output that is NULL is not written.
+template <int NS>
+__global__ void __launch_bounds__(256)
+rays_intr_bwd_finish_kernel(const double* __restrict__ partials, int n_partials, double sx, double sy, float* __restrict__ g_c2w,
+                            float* __restrict__ g_intr) {
+  __shared__ double sh[4];
+  double tot[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const double v = (int)threadIdx.x < n_partials ? partials[threadIdx.x * NS + k] : 0.0;
+    tot[k] = block_sum(v, sh);
+  }
+  if (threadIdx.x != 0) return;
+  if constexpr (NS == CAM_SUMS) {
+    if (g_c2w != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) g_c2w[k] = (float)tot[k];
+    }
+    if (g_intr != nullptr) {
+      g_intr[0] = (float)((tot[12] + tot[NS - 2] * sx) + tot[NS - 1] * sy);
+      g_intr[1] = (float)tot[13]; g_intr[2] = (float)tot[14]; g_intr[3] = (float)tot[15];
+    }
+  } else {
+    g_intr[0] = (float)(tot[NS - 2] * sx + tot[NS - 1] * sy);
   }
 }
 
@@ -389,50 +484,87 @@ static snx::Camera make_camera(float fx, float fy, float cx, float cy, int conve
   return snx::Camera{fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near, (float)(2.0 * (double)ndc_near)};
 }
 
+// intr != NULL in the four launches below: the intrinsics (one focal length for the NDC map on its own) are read from DEVICE memory by
+// the kernel and the floats given for them are ignored; H, W then form a_x, a_y on the device.
 extern "C" int sn_generate_rays_cam_launch(const float* c2w, float fx, float fy, float cx, float cy, int convention, int ndc, float ax,
                                            float ay, float ndc_near, float near, float far, int x0, int y0, int sx, int sy, int pw,
-                                           int ph, float* rays, hipStream_t stream) {
+                                           int ph, float* rays, const float* intr, int H, int W, hipStream_t stream) {
+  using namespace snx;
   const long total = (long)pw * ph;
   if (total <= 0) return 0;
   long blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(snx::generate_rays_cam_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, c2w,
-                     make_camera(fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near), near, far, snx::Window{x0, y0, sx, sy, pw, ph}, rays);
+  const Camera cam = make_camera(fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near);
+  const Window win{x0, y0, sx, sy, pw, ph};
+  if (intr != nullptr)
+    hipLaunchKernelGGL(generate_rays_cam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, c2w, cam, intr, H, W, near, far, win, rays);
+  else
+    hipLaunchKernelGGL(generate_rays_cam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, c2w, cam, intr, H, W, near, far, win, rays);
   return (int)hipGetLastError();
 }
 
+extern "C" long sn_camera_backward_workspace_bytes_impl() { return (long)snx::RAYS_BWD_BLOCKS * snx::CAM_SUMS * sizeof(double); }
+// intr == NULL: g_intr is not used, the workspace is that of sn_generate_rays_backward and c2w is read only with ndc
 extern "C" int sn_generate_rays_cam_backward_launch(const float* g_rays, const float* c2w, float fx, float fy, float cx, float cy,
                                                     int convention, int ndc, float ax, float ay, float ndc_near, int x0, int y0, int sx,
-                                                    int sy, int pw, int ph, void* workspace, float* g_c2w, hipStream_t stream) {
+                                                    int sy, int pw, int ph, void* workspace, float* g_c2w, const float* intr, int H, int W,
+                                                    float* g_intr, hipStream_t stream) {
   using namespace snx;
   const long total = (long)pw * ph;
   long blocks = (total + 255) / 256;
-  if (blocks < 1) blocks = 1;                    // an empty window still writes its 12 zeros
+  if (blocks < 1) blocks = 1;                    // an empty window still writes its zeros
   if (blocks > RAYS_BWD_BLOCKS) blocks = RAYS_BWD_BLOCKS;
   double* partials = reinterpret_cast<double*>(workspace);
-  hipLaunchKernelGGL(rays_cam_bwd_partials_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, c2w,
-                     make_camera(fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near), Window{x0, y0, sx, sy, pw, ph}, partials);
-  hipLaunchKernelGGL(rays_bwd_finish_kernel, dim3(1), dim3(256), 0, stream, partials, (int)blocks, g_c2w);
+  const Camera cam = make_camera(fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near);
+  const Window win{x0, y0, sx, sy, pw, ph};
+  if (intr != nullptr) {
+    hipLaunchKernelGGL(rays_cam_bwd_partials_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, c2w, cam, intr, H, W, win,
+                       partials);
+    hipLaunchKernelGGL(rays_intr_bwd_finish_kernel<CAM_SUMS>, dim3(1), dim3(256), 0, stream, partials, (int)blocks, -2.0 / (double)W,
+                       -2.0 / (double)H, g_c2w, g_intr);
+  } else {
+    hipLaunchKernelGGL(rays_cam_bwd_partials_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, c2w, cam, intr, H, W, win,
+                       partials);
+    hipLaunchKernelGGL(rays_bwd_finish_kernel, dim3(1), dim3(256), 0, stream, partials, (int)blocks, g_c2w);
+  }
   return (int)hipGetLastError();
 }
 
 extern "C" int sn_ndc_rays_launch(const float* rays_in, long n_rays, float ax, float ay, float ndc_near, float* rays_out,
-                                  hipStream_t stream) {
+                                  const float* focal, int H, int W, hipStream_t stream) {
+  using namespace snx;
   if (n_rays <= 0) return 0;
   long blocks = (n_rays + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(snx::ndc_rays_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, n_rays,
-                     make_camera(1.0f, 1.0f, 0.0f, 0.0f, 0, 1, ax, ay, ndc_near), rays_out);
+  const Camera cam = make_camera(1.0f, 1.0f, 0.0f, 0.0f, 0, 1, ax, ay, ndc_near);
+  if (focal != nullptr)
+    hipLaunchKernelGGL(ndc_rays_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, n_rays, cam, focal, H, W, rays_out);
+  else
+    hipLaunchKernelGGL(ndc_rays_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, n_rays, cam, focal, H, W, rays_out);
   return (int)hipGetLastError();
 }
 
+// focal != NULL: g_focal (1 float) is written as well, through workspace (sn_camera_backward_workspace_bytes); no rays: g_focal = 0
 extern "C" int sn_ndc_rays_backward_launch(const float* rays_in, const float* g_rays_out, long n_rays, float ax, float ay,
-                                           float ndc_near, float* g_rays_in, hipStream_t stream) {
-  if (n_rays <= 0) return 0;
+                                           float ndc_near, float* g_rays_in, const float* focal, int H, int W, void* workspace,
+                                           float* g_focal, hipStream_t stream) {
+  using namespace snx;
+  const Camera cam = make_camera(1.0f, 1.0f, 0.0f, 0.0f, 0, 1, ax, ay, ndc_near);
   long blocks = (n_rays + 255) / 256;
+  if (focal != nullptr) {
+    if (blocks < 1) blocks = 1;
+    if (blocks > RAYS_BWD_BLOCKS) blocks = RAYS_BWD_BLOCKS;
+    double* partials = reinterpret_cast<double*>(workspace);
+    hipLaunchKernelGGL(ndc_rays_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, g_rays_out, n_rays, cam, focal, H,
+                       W, g_rays_in, partials);
+    hipLaunchKernelGGL(rays_intr_bwd_finish_kernel<NDC_SUMS>, dim3(1), dim3(256), 0, stream, partials, (int)blocks, -2.0 / (double)W,
+                       -2.0 / (double)H, (float*)nullptr, g_focal);
+    return (int)hipGetLastError();
+  }
+  if (n_rays <= 0) return 0;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(snx::ndc_rays_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, g_rays_out, n_rays,
-                     make_camera(1.0f, 1.0f, 0.0f, 0.0f, 0, 1, ax, ay, ndc_near), g_rays_in);
+  hipLaunchKernelGGL(ndc_rays_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, g_rays_out, n_rays, cam, focal, H, W,
+                     g_rays_in, (double*)nullptr);
   return (int)hipGetLastError();
 }
 

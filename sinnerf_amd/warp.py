@@ -205,6 +205,7 @@ def unseen_view_batch(ref_view, ref_depth, K, ref_c2w, side_c2w, near, far, wind
     new, new_depth, _, _, _ = _warp(data, depth, ref_P, src_P, mode, eps, (x0, y0, sx, sy, pw, ph), want_mask=False)
     _, depth_full, mask_full, _, _ = _warp(None, depth, ref_P, src_P, mode, eps, None)
     idx, n_landed = select_landed(mask_full, u_proj)
+    focal, center = (v.detach() if torch.is_tensor(v) else v for v in (focal, center))       # labels: no gradient, device tensors stay there
     cam = dict(center=center, convention=convention, ndc_near=ndc_near)
     side_pose = side_c2w[:3].detach().float()
     rays_full = get_rays(H, W, focal, side_pose, near, far, (x0, y0, sx, sy, pw, ph), **cam)
