@@ -396,6 +396,32 @@ int sn_ndc_rays_dev_backward(const float* rays_in, const float* g_rays_out, long
 int sn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
                  float beta2, float eps, float weight_decay, int step, void* stream);
 
+/* ---- the reference's other optimisers (opt.py --optimizer {sgd, radam, ranger}; utils/__init__.py:16-27) over the same flat fp32
+ * buffers, one launch each, in place (additive within ABI 5).  n >= 0 elements (n = 0: nothing is launched, returns 0); buffers are
+ * DEVICE fp32 of n elements and must not overlap.  The scalars are doubles the CALLER computes on the host (from its own step
+ * counter: nothing is read back from the device); each is rounded to fp32 once, as torch rounds a Python scalar, and the arithmetic
+ * is fp32 with one rounding per operation.
+ *
+ * sn_sgd_step -- torch.optim.SGD, dampening 0, no Nesterov:
+ *   g += weight_decay p (when != 0) ; buf = momentum buf + g ; p -= lr buf.  A zero-initialised buf reproduces torch's first step
+ *   (buf = g).  momentum == 0: p -= lr g, momentum_buf is not touched and may be NULL.
+ *
+ * sn_radam_step -- the element-wise part of utils/optimizers.py:62-104, in that order:
+ *   v = v beta2 + (1 - beta2) g g ; m = m beta1 + (1 - beta1) g                    (always)
+ *   p -= decay p (when decay != 0; decay = weight_decay lr: decoupled, applied to the parameter)
+ *   p -= step_coeff m / (sqrt(v) + eps) when rectified != 0, else p -= step_coeff m         (step_coeff = step_size lr)
+ *   step_coeff < 0: no parameter update this step and no decay (degenerated_to_sgd=False below the N_sma threshold, :86-87, 99).
+ *
+ * sn_ranger_step -- utils/optimizers.py:393-437: the same moments and update with the decay applied on every step (:416-418;
+ *   step_coeff < 0 is refused), then, when sync != 0, the lookahead of :431-437 in the same launch:
+ *   slow += alpha (p - slow) ; p = slow.  slow (n) is read and written only when sync != 0, but must always be given.            */
+int sn_sgd_step(float* params, const float* grads, float* momentum_buf, long n, double lr, double momentum, double weight_decay,
+                void* stream);
+int sn_radam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, double beta1, double beta2, double eps,
+                  double decay, double step_coeff, int rectified, void* stream);
+int sn_ranger_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, double beta1, double beta2, double eps,
+                   double decay, double step_coeff, int rectified, float* slow, double alpha, int sync, void* stream);
+
 /* ---- losses on the rendered rays, forward + gradients in two launches: MSELoss (losses.py:12-22: nn.MSELoss 'mean' of
  * rgb_coarse and rgb_fine against the targets), SL1Loss (models/sinnerf.py:32-42: nn.SmoothL1Loss 'mean', beta 1, of
  * depth_coarse and depth_fine -- call sites :310-319) and psnr (metrics.py:5-15).

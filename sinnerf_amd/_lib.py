@@ -60,6 +60,10 @@ SIGNATURES = {
     "sn_weight_grads": (_int, [c_vp, c_fp, c_vp, _long, _int, c_vp, ctypes.POINTER(c_vp), _int, c_vp]),
     "sn_generate_rays": (_int, [c_fp, _int, _int, _float, _float, _float, _int, _int, _int, _int, _int, _int, c_fp, c_vp]),
     "sn_adam_step": (_int, [c_fp, c_fp, c_fp, c_fp, _long, _float, _float, _float, _float, _float, _int, c_vp]),
+    "sn_sgd_step": (_int, [c_fp, c_fp, c_fp, _long, _double, _double, _double, c_vp]),
+    "sn_radam_step": (_int, [c_fp, c_fp, c_fp, c_fp, _long, _double, _double, _double, _double, _double, _int, c_vp]),
+    "sn_ranger_step": (_int, [c_fp, c_fp, c_fp, c_fp, _long, _double, _double, _double, _double, _double, _int, c_fp, _double, _int,
+                              c_vp]),
     "sn_render_loss_workspace_bytes": (_long, []),
     "sn_render_loss": (_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_vp, _int, _long, _float, _float, c_fp, c_fp, c_fp, c_fp,
                               c_vp, c_fp, c_vp]),

@@ -336,6 +336,27 @@ int sn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_a
                              (hipStream_t)stream);
 }
 
+// ---- the reference's other optimisers (sn_optim.hip): every refusal below returns before a launch
+int sn_sgd_step(float* params, const float* grads, float* momentum_buf, long n, double lr, double momentum, double weight_decay,
+                void* stream) {
+  if (!params || !grads || n < 0 || (momentum != 0.0 && !momentum_buf)) return SN_E_BADARG;
+  return sn_sgd_step_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, (hipStream_t)stream);
+}
+
+int sn_radam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, double beta1, double beta2, double eps,
+                  double decay, double step_coeff, int rectified, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || n < 0) return SN_E_BADARG;
+  return sn_radam_step_launch(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, decay, step_coeff, rectified, nullptr, 0.0, 0,
+                              (hipStream_t)stream);
+}
+
+int sn_ranger_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, double beta1, double beta2, double eps,
+                   double decay, double step_coeff, int rectified, float* slow, double alpha, int sync, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !slow || n < 0 || step_coeff < 0.0) return SN_E_BADARG;
+  return sn_radam_step_launch(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, decay, step_coeff, rectified, slow, alpha, sync,
+                              (hipStream_t)stream);
+}
+
 long sn_render_loss_workspace_bytes(void) { return sn_render_loss_workspace_bytes_impl(); }
 
 int sn_render_loss(const float* rgb_coarse, const float* rgb_fine, const float* depth_coarse, const float* depth_fine,

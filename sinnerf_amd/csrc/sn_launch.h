@@ -175,6 +175,11 @@ int sn_ndc_rays_backward_launch(const float* rays_in, const float* g_rays_out, l
                                 hipStream_t stream);
 int sn_adam_step_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                         float wd, int step, hipStream_t stream);
+// the other optimisers of the reference over the same flat buffers (sn_optim.hip); the scalars arrive in double and are rounded to fp32 once.
+// sn_radam_step_launch: slow == nullptr is RAdam, otherwise Ranger (lookahead into slow when sync != 0)
+int sn_sgd_step_launch(float* p, const float* g, float* buf, long n, double lr, double momentum, double wd, hipStream_t stream);
+int sn_radam_step_launch(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, double decay,
+                         double step_coeff, int rectified, float* slow, double alpha, int sync, hipStream_t stream);
 long sn_render_loss_workspace_bytes_impl();
 int sn_render_loss_launch(const float* rgb_c, const float* rgb_f, const float* depth_c, const float* depth_f,
                           const float* rgb_gt, const float* depth_gt, const unsigned char* mask, int mask_mode, long n,

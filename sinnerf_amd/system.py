@@ -20,7 +20,7 @@ import torch
 from torch import nn
 
 from .nerf import Embedding, NeRF
-from .optim import FlatAdam
+from .optim import FlatAdam, FlatOptimizer, FlatSGD, GradualWarmupScheduler, get_optimizer, get_scheduler
 from .parallel import all_reduce_mean_grads, broadcast_parameters
 from .losses import inverse_depth_smoothness_loss, loss_dict, psnr, render_loss      # noqa: F401  (psnr re-exported: metrics.py:14-15)
 from .rendering import render_rays
@@ -34,7 +34,10 @@ DEFAULT_HPARAMS = dict(N_samples=64, N_importance=64, use_disp=False, perturb=1.
                        dis_weight=0.0, dloss="hinge", patch_hw=None,
                        # the reference's losses on the rendered patches (opt.py --patch_loss / --depth_smooth_weight / --proj_weight /
                        # --dataset_name; patch_losses below).  The defaults add no term
-                       patch_loss="mse", depth_smooth_weight=0.0, proj_weight=1.0, dataset_name=None)
+                       patch_loss="mse", depth_smooth_weight=0.0, proj_weight=1.0, dataset_name=None,
+                       # the reference's optimiser and schedule flags with its defaults (opt.py:45-71; sinnerf_amd/optim.py builds them)
+                       optimizer="adam", momentum=0.9, lr_scheduler="steplr", num_epochs=80, poly_exp=0.9, warmup_multiplier=1.0,
+                       warmup_epochs=0)
 
 
 
@@ -45,7 +48,13 @@ def rebuild_scheduler(sch, new_opt):
     A ``MultiStepLR`` is constructed fresh (its constructor takes one initial step: ``last_epoch`` 0, the group's current lr kept)
     and then given the old one's ``state_dict`` -- epoch counter, step count, ``_last_lr``, milestones.  Passing
     ``last_epoch=sch.last_epoch`` to the constructor instead would resume one epoch AHEAD (the initial step increments it), so every
-    milestone of ``utils/__init__.py:34-36`` would fire one step early.  Other scheduler types are re-pointed in place."""
+    milestone of ``utils/__init__.py:34-36`` would fire one step early.  Other scheduler types are re-pointed in place; a warm-up
+    wrapper is re-pointed together with the schedule it wraps."""
+    if isinstance(sch, GradualWarmupScheduler):
+        if sch.after_scheduler is not None:
+            sch.after_scheduler = rebuild_scheduler(sch.after_scheduler, new_opt)
+        sch.optimizer = new_opt
+        return sch
     if isinstance(sch, torch.optim.lr_scheduler.MultiStepLR):
         lrs = [g["lr"] for g in new_opt.param_groups]
         ns = torch.optim.lr_scheduler.MultiStepLR(new_opt, milestones=sorted(sch.milestones.elements()), gamma=sch.gamma)
@@ -138,23 +147,27 @@ class SinNeRFSystem(nn.Module):
 
     # ---- sinnerf.py:202-210 + utils/__init__.py:11-57 -----------------------------------------------------------
     def configure_optimizers(self):
-        """Adam(lr, eps=1e-8, weight_decay) + MultiStepLR as ``get_optimizer`` / ``get_scheduler`` build them
-        (utils/__init__.py:19-21, 27-31).  The optimiser is ``FlatAdam`` (a ``torch.optim.Optimizer``): parameters and
-        gradients of both NeRFs live in flat buffers, one step = the single all-reduce + one ``sn_adam_step`` launch."""
+        """``hparams.optimizer`` (adam: lr, eps=1e-8, weight_decay) + ``hparams.lr_scheduler`` (steplr: MultiStepLR) as
+        ``get_optimizer`` / ``get_scheduler`` build them (utils/__init__.py:11-52; sinnerf_amd/optim.py).  The optimiser is the flat
+        class of its kind (a ``torch.optim.Optimizer``): parameters and gradients of both NeRFs live in flat buffers, one step = the
+        single all-reduce + one launch.  The defaults give ``FlatAdam`` + ``MultiStepLR``."""
         hp = self.hparams
         params = [p for m in self.models for p in m.parameters()]
         if params[0].is_cuda:
-            self.optimizer = FlatAdam(self.models, lr=hp.lr, eps=1e-8, weight_decay=hp.weight_decay)
+            self.optimizer = get_optimizer(hp, self.models)
             self._flat = self.optimizer.grads
         else:       # module still on the host (Lightning calls configure_optimizers before .to(device) in some versions):
-            # the reference's own optimiser; the render path itself has no CPU form and raises on CPU tensors
-            self.optimizer = torch.optim.Adam(params, lr=hp.lr, eps=1e-8, weight_decay=hp.weight_decay)
-        scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=hp.decay_step, gamma=hp.decay_gamma)
+            # the reference's own Adam / SGD (upgraded by the first train_step on the device); radam / ranger have no host form and
+            # raise.  The render path itself has no CPU form and raises on CPU tensors
+            self.optimizer = get_optimizer(hp, self.models, flat=False)
+        scheduler = get_scheduler(hp, self.optimizer)
         self._schedulers = [scheduler]
         self.__dict__.pop("_step_graphs", None)      # captured steps bake in the old flat-buffer addresses
         opts = [self.optimizer]
         if self.D is not None and hp.dis_weight > 0:                             # sinnerf.py:207-208: get_optimizer(hparams, [self.D], rate=0.2)
-            self.opt_d = torch.optim.Adam(self.D.parameters(), lr=hp.lr * 0.2, eps=1e-8, weight_decay=hp.weight_decay)
+            # the same kind: stock Adam / SGD, which stay on PyTorch with the discriminator; the flat class for radam / ranger, without
+            # an exchange of its own (train_step_adversarial averages D's gradients itself)
+            self.opt_d = get_optimizer(hp, [self.D], rate=0.2, flat=False, all_reduce=False)
             opts.append(self.opt_d)
         return opts, [scheduler]
 
@@ -301,12 +314,12 @@ class SinNeRFSystem(nn.Module):
 
     # ---- minimal driver: one optimisation step with the single flat all-reduce -----------------------
     def _ensure_flat_optimizer(self):
-        """``configure_optimizers`` may have run while the module was still on the host (stock Adam, no flat buffers, NO
-        gradient exchange).  Once the parameters are on the device the optimiser is rebuilt as ``FlatAdam`` -- carrying over
-        the hyper-parameters a scheduler may already have changed -- so that ``train_step`` always ends in the one flat
-        all-reduce.  Adam state accumulated by a host-side optimiser is refused rather than silently dropped."""
+        """``configure_optimizers`` may have run while the module was still on the host (stock Adam / SGD, no flat buffers, NO
+        gradient exchange).  Once the parameters are on the device the optimiser is rebuilt as ``FlatAdam`` / ``FlatSGD`` -- carrying
+        over the hyper-parameters a scheduler may already have changed -- so that ``train_step`` always ends in the one flat
+        all-reduce.  State accumulated by a host-side optimiser is refused rather than silently dropped."""
         opt = getattr(self, "optimizer", None)
-        if isinstance(opt, FlatAdam):
+        if isinstance(opt, FlatOptimizer):
             return opt
         params = [p for m in self.models for p in m.parameters()]
         if not params[0].is_cuda:
@@ -321,10 +334,15 @@ class SinNeRFSystem(nn.Module):
             self.configure_optimizers()
             return self.optimizer
         if any(len(st) for st in opt.state.values()):
-            raise RuntimeError("SinNeRFSystem: the host-side optimiser already holds Adam state; call configure_optimizers() "
-                               "again after .to(device) (or load its state into the new FlatAdam) instead of stepping on")
+            raise RuntimeError("SinNeRFSystem: the host-side optimiser already holds state; call configure_optimizers() "
+                               "again after .to(device) (or load its state into the new flat optimiser) instead of stepping on")
         g = opt.param_groups[0]
-        new = FlatAdam(self.models, lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"])
+        if isinstance(opt, torch.optim.SGD):
+            if g["dampening"] != 0 or g["nesterov"] or g.get("maximize", False):
+                raise RuntimeError("SinNeRFSystem: FlatSGD mirrors torch.optim.SGD without dampening, Nesterov momentum or maximize")
+            new = FlatSGD(self.models, lr=g["lr"], momentum=g["momentum"], weight_decay=g["weight_decay"])
+        else:
+            new = FlatAdam(self.models, lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"])
         if "initial_lr" in g:
             new.param_groups[0]["initial_lr"] = g["initial_lr"]
         # the scheduler is REBUILT on the new optimiser (patching `.optimizer` would leave its step-order bookkeeping --
@@ -412,7 +430,7 @@ class SinNeRFSystem(nn.Module):
         hp = self.hparams
         # a captured step bakes in the flat parameter / gradient buffers and every hyper-parameter the launches read
         key = (tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in tensors.items())),
-               self.optimizer.flat.data_ptr() if isinstance(self.optimizer, FlatAdam) else None,
+               self.optimizer.flat.data_ptr() if isinstance(self.optimizer, FlatOptimizer) else None,
                self._flat.flat.data_ptr() if self._flat is not None else None,
                hp.N_samples, hp.N_importance, hp.use_disp, hp.perturb, hp.noise_std, hp.chunk, hp.depth_weight,
                hp.compute_dtype, self.white_back, self.training, hp.patch_loss, hp.depth_smooth_weight, hp.proj_weight,
@@ -420,7 +438,7 @@ class SinNeRFSystem(nn.Module):
         cache = self.__dict__.setdefault("_step_graphs", {})
         hit = cache.get(key)
         if hit is None:
-            if not isinstance(self.optimizer, FlatAdam):
+            if not isinstance(self.optimizer, FlatOptimizer):
                 raise RuntimeError("train_step(graph=True) needs the flat optimiser (parameters on a ROCm device)")
             static = {k: v.clone() for k, v in tensors.items()}
             cur = torch.cuda.current_stream()
@@ -446,6 +464,6 @@ class SinNeRFSystem(nn.Module):
     def replica_checksum(self):
         """fp64 sum and sum of squares of the flat parameter buffer: equal on every rank iff the replicas are identical
         (what the bench's multi-GPU training leg asserts after a few steps)."""
-        flat = self.optimizer.flat.double() if isinstance(getattr(self, "optimizer", None), FlatAdam) else \
+        flat = self.optimizer.flat.double() if isinstance(getattr(self, "optimizer", None), FlatOptimizer) else \
             torch.cat([p.detach().reshape(-1) for m in self.models for p in m.parameters()]).double()
         return torch.stack([flat.sum(), (flat * flat).sum()])
