@@ -29,7 +29,7 @@ extern "C" {
                             *    sn_generate_rays_cam, sn_generate_rays_cam_backward, sn_ndc_rays, sn_ndc_rays_backward
                             *    and, with the intrinsics in device memory and their gradients, sn_generate_rays_cam_dev,
                             *    sn_generate_rays_cam_dev_backward, sn_camera_backward_workspace_bytes, sn_ndc_rays_dev,
-                            *    sn_ndc_rays_dev_backward) */
+                            *    sn_ndc_rays_dev_backward; the density-gradient entries sn_point_grads, sn_point_grads_wsum) */
 
 #define SN_DTYPE_F32 0  /* v_mfma_f32_32x32x2_f32, exact fp32                                          */
 #define SN_DTYPE_BF16 1 /* v_mfma_f32_32x32x16_bf16, bf16 operands / fp32 accumulate                    */
@@ -278,6 +278,35 @@ int sn_ray_grads(const float* w1, const float* w5, const float* wdir, int dtype,
 int sn_composite_backward_rays(const float* raw, const float* z_vals, const float* rays, const float* noise, float noise_std,
                                long n_rays, int n_samples, int white_back, const float* g_rgb, const float* g_depth,
                                const float* g_weights, float* g_raw, float* g_rays, void* stream);
+
+/* ==== gradients with respect to a POSITION (additive within ABI 5) ============================================
+ * What autograd derives from models/nerf.py:36-41 + :122-148 for d(out)/d(xyz) at every sample point, kept PER POINT: the
+ * contraction and the Embedding derivative of sn_ray_grads without its direction part and without its sum over the samples of a ray.
+ *   g_emb_xyz = G0 . W1 + G4 . W5[:, 0:63]
+ *   g_xyz[p]  = ge[0:3] + sum_k 2^k (cos(2^k x) ge[3+6k : 6+6k] - sin(2^k x) ge[6+6k : 9+6k])   (k < 10; sin / cos recomputed)
+ * (sin / cos from the forward's range reduction with its one rounding compensated, so a factor near one of its zeros keeps its
+ * relative accuracy: a per-point gradient has no sum over samples behind which an absolute 2e-7 of the angle could hide)
+ * at x = fl(o + fl(d z)), the fp32 position the forward embedded (rendering.py:284-285), p = (ray, sample) in row order.  With g_acts
+ * from sn_mlp_backward_chain run on g_raw = (0, 0, 0, 1) for every point this is the gradient of the raw sigma (nerf.py:136), the
+ * un-normalised surface normal up to sign; any other g_raw gives the position gradient of that linear functional of the output.
+ * w1, w5: the raw fp32 parameter tensors as for sn_ray_grads.  g_acts / slot_rows: as written by sn_mlp_backward_chain; only slots 0
+ * and 4 and only rows < n_rays * n_samples are read (pad rows may hold anything, NaN included).  dtype names the LAYOUT that chain left,
+ * exactly as for sn_ray_grads: SN_DTYPE_F32 / SN_DTYPE_BF16 (fp32 rows), SN_DTYPE_BF16_STATE (bf16 rows), SN_DTYPE_BF16X3 ((hi, lo)
+ * pairs, the value used is hi + lo); anything else, flag bits included, is SN_E_UNSUPPORTED.  fp32 arithmetic
+ * (v_mfma_f32_32x32x2_f32) whatever the layout.  g_xyz (n_rays * n_samples, 4) = [gx, gy, gz, 0] is WRITTEN (not accumulated), one
+ * 16-byte store per point; no atomics, no workspace: two calls give the same bits.  n_samples in 1..1024 (SN_E_BADSHAPE), slot_rows >=
+ * n_rays * n_samples (SN_E_BADSHAPE), a null pointer is SN_E_BADARG; n_rays <= 0 launches nothing and returns 0.                    */
+int sn_point_grads(const float* w1, const float* w5, int dtype, const void* g_acts, long slot_rows, const float* rays,
+                   const float* z_vals, long n_rays, int n_samples, float* g_xyz, void* stream);
+
+/* ---- the weighted sum of the per-point gradients over the samples of each ray (the numerator of a normal map):
+ *   g_sum[r] = [sum_s weights[r, s] g_xyz[r, s, 0:3], 0]
+ * g_xyz (n_rays * n_samples, 4) as written by sn_point_grads, weights (n_rays, n_samples) e.g. the compositing weights of
+ * sn_composite_forward.  One wave per ray: products and sums in fp64 (a product of two fp32 values is exact there), lane l adds samples
+ * l, l + 64, ... in order, then a butterfly over the lanes; ONE rounding to fp32.  Fixed order, no atomics: two calls give the same
+ * bits.  g_sum (n_rays, 4) is written.  n_samples in 1..1024 (SN_E_BADSHAPE); a null pointer is SN_E_BADARG; n_rays <= 0 launches
+ * nothing and returns 0.                                                                                                     */
+int sn_point_grads_wsum(const float* g_xyz, const float* weights, long n_rays, int n_samples, float* g_sum, void* stream);
 
 /* ---- models/nerf.py:105-148  NeRF.forward(x, sigma_only) on an already embedded matrix --------------------
  * x (n_rows, ld) with columns [0,63) = embedded xyz and [63,90) = embedded dir (ignored when sigma_only).   */

@@ -79,6 +79,8 @@ SIGNATURES = {
     "sn_composite_backward": (_int, [c_fp, c_fp, c_fp, c_fp, _float, _long, _int, _int, c_fp, c_fp, c_fp, c_fp, c_vp]),
     "sn_ray_grads_workspace_bytes": (_long, [_long, _int]),
     "sn_ray_grads": (_int, [c_fp, c_fp, c_fp, _int, c_vp, _long, c_fp, c_fp, _long, _int, c_vp, c_fp, c_vp]),
+    "sn_point_grads": (_int, [c_fp, c_fp, _int, c_vp, _long, c_fp, c_fp, _long, _int, c_fp, c_vp]),
+    "sn_point_grads_wsum": (_int, [c_fp, c_fp, _long, _int, c_fp, c_vp]),
     "sn_composite_backward_rays": (_int, [c_fp, c_fp, c_fp, c_fp, _float, _long, _int, _int, c_fp, c_fp, c_fp, c_fp, c_fp, c_vp]),
     "sn_generate_rays_backward_workspace_bytes": (_long, []),
     "sn_generate_rays_backward": (_int, [c_fp, _int, _int, _float, _int, _int, _int, _int, _int, _int, c_vp, c_fp, c_vp]),

@@ -9,6 +9,8 @@ an ordinary autograd graph whose leaves are the ``NeRF`` parameters (DDP hooks /
                                                                  ->  sn_ray_grads (only when ``rays`` requires grad)
   _CompositeFn  sn_composite_forward  ->  sn_composite_backward  (sn_composite_backward_rays when ``rays`` requires grad)
 
+``_chain_state`` is the first two launches of ``_MLPFn`` for a GIVEN upstream gradient, outside autograd (``geometry``: density gradients).
+
 ``sample_pdf`` is detached as in the reference (``rendering.py:312``); the sample depths are data (no gradient).  The rays are
 differentiable in their origins and directions (columns 0..5) when they require grad: pose refinement / registration optimise
 ``c2w`` through ``ray_utils.get_rays`` -> ``render_rays``.  near / far (columns 6, 7) are constants: their gradient is zero.
@@ -195,6 +197,37 @@ class _MLPFn(torch.autograd.Function):
             grads = _weight_grads(model, acts, emb, G, needs) if any(needs) else [None] * len(needs)
             g_rays = _ray_grads(model, G, rows, *ctx.saved_tensors[3:]) if ctx.rays_grad else None
         return (None, g_rays, None, *grads)
+
+
+def _chain_state(model, rays, z_vals, g_raw):
+    """Training forward + backward chain of one (rays, z_vals) pass for a given upstream gradient ``g_raw`` (P, 4), outside autograd:
+    the state allocation and the two launches of ``_MLPFn`` (same kernels, same flags) without the weight-gradient stage.  Returns
+    ``(out (N, S, 4), G, rows, code)``: ``G`` holds the pre-activation gradients in the layout ``code`` names for ``sn_ray_grads`` /
+    ``sn_point_grads``; its pad rows (>= N S) are not zero-filled -- neither of those entries reads them.  Used by ``geometry``."""
+    n, s = z_vals.shape
+    P = n * s
+    dev = rays.device
+    code = dtype_code(model.compute_dtype)
+    bf16 = code == _lib.SN_DTYPE_BF16
+    if bf16:
+        code = _lib.SN_DTYPE_BF16_STATE
+    out = torch.empty((n, s, 4), dtype=torch.float32, device=dev)
+    tile = 256 if bf16 else 128
+    rows = -(-P // tile) * tile
+    state = torch.bfloat16 if bf16 else torch.float32
+    acts = torch.empty((10, rows, 256), dtype=state, device=dev)
+    emb16 = bf16 and EMB_BF16 and not COMPILER_SCHEDULED and P < 2 ** 31 - 256 and _emb16_supported()
+    emb = torch.empty((rows, 128), dtype=torch.bfloat16 if emb16 else torch.float32, device=dev)
+    flags = _sched_flag() | (_lib.SN_DTYPE_EMB_BF16 if emb16 else 0)
+    _lib.check(_lib.lib.sn_mlp_forward_train(_lib.ptr(model.packed()), model.kernel_dtype(code) | flags, _lib.ptr(rays), _lib.ptr(z_vals), n, s,
+                                             _lib.ptr(out), _lib.ptr(acts), _lib.ptr(emb), rows, _lib.stream_ptr()),
+               "sn_mlp_forward_train")
+    G = torch.empty((10, rows, 256), dtype=state, device=dev)
+    g_o = torch.empty((P, 4), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib.sn_mlp_backward_chain(_lib.ptr(model.packed_bwd(model.compute_dtype)), model.kernel_dtype(code) | _sched_flag(),
+                                              _lib.ptr(acts), _lib.ptr(out), _lib.ptr(g_raw), P, rows, _lib.ptr(G),
+                                              _lib.ptr(g_o), _lib.stream_ptr()), "sn_mlp_backward_chain")
+    return out, G, rows, _state_code(model, G) & ~_lib.SN_DTYPE_EMB_BF16
 
 
 class _CompositeFn(torch.autograd.Function):

@@ -512,6 +512,24 @@ int sn_ray_grads(const float* w1, const float* w5, const float* wdir, int dtype,
                              (hipStream_t)stream);
 }
 
+int sn_point_grads(const float* w1, const float* w5, int dtype, const void* g_acts, long slot_rows, const float* rays,
+                   const float* z_vals, long n_rays, int n_samples, float* g_xyz, void* stream) {
+  if (!w1 || !w5 || !g_acts || !rays || !z_vals || !g_xyz) return SN_E_BADARG;
+  if (n_samples < 1 || n_samples > 1024) return SN_E_BADSHAPE;
+  if (n_rays > 0 && slot_rows < n_rays * (long)n_samples) return SN_E_BADSHAPE;
+  // the layout sn_mlp_backward_chain(dtype) left g_acts in, as for sn_ray_grads: no flag bits
+  Dtype d;
+  if (!parse_dtype(dtype, 0, TRAINABLE, &d)) return SN_E_UNSUPPORTED;
+  const int layout = d.base == SN_DTYPE_BF16_STATE ? 1 : d.base == SN_DTYPE_BF16X3 ? 2 : 0;      // fp32 rows / bf16 rows / x3 pairs
+  return sn_point_grads_launch(w1, w5, layout, g_acts, slot_rows, rays, z_vals, n_rays, n_samples, g_xyz, (hipStream_t)stream);
+}
+
+int sn_point_grads_wsum(const float* g_xyz, const float* weights, long n_rays, int n_samples, float* g_sum, void* stream) {
+  if (!g_xyz || !weights || !g_sum) return SN_E_BADARG;
+  if (n_samples < 1 || n_samples > 1024) return SN_E_BADSHAPE;
+  return sn_point_grads_wsum_launch(g_xyz, weights, n_rays, n_samples, g_sum, (hipStream_t)stream);
+}
+
 long sn_generate_rays_backward_workspace_bytes(void) { return sn_generate_rays_backward_workspace_bytes_impl(); }
 
 int sn_generate_rays_backward(const float* g_rays, int H, int W, float focal, int x0, int y0, int stride_x, int stride_y,

@@ -189,6 +189,11 @@ long sn_ray_grads_workspace_bytes_impl(long n_rays, int n_samples);
 int sn_ray_grads_launch(const float* w1, const float* w5, const float* wdir, int layout, const void* g_acts, long slot_rows,
                         const float* rays, const float* z_vals, long n_rays, int n_samples, void* workspace, float* g_rays,
                         hipStream_t stream);
+// ... and the per-point position gradients with their weighted sum over a ray's samples (sn_ray_grad.hip)
+int sn_point_grads_launch(const float* w1, const float* w5, int layout, const void* g_acts, long slot_rows, const float* rays,
+                          const float* z_vals, long n_rays, int n_samples, float* g_xyz, hipStream_t stream);
+int sn_point_grads_wsum_launch(const float* g_xyz, const float* weights, long n_rays, int n_samples, float* g_sum,
+                               hipStream_t stream);
 // the losses on the rendered patches (sn_patch_loss.hip); *_blocks_impl: partial records the first kernel writes
 long sn_patch_loss_blocks_impl(int B, int H, int W, int C, int use_ssim);
 long sn_patch_loss_workspace_bytes_impl(int B, int H, int W, int C, int use_ssim);

@@ -289,3 +289,170 @@ extern "C" int sn_ray_grads_launch(const float* w1, const float* w5, const float
                      g_rays);
   return (int)hipGetLastError();
 }
+
+// ---- gradients with respect to a POSITION: sn_point_grads / sn_point_grads_wsum --------------------------------------------------------
+// The per-point value ray_grad_points_kernel holds before the sum over a ray's samples takes it away, kept: d(out)/d(xyz) of every
+// sample point for the upstream gradient the chain was run with (g_raw = (0, 0, 0, 1): the gradient of the raw sigma, nerf.py:136).
+//
+//   point_grad_kernel        ray_grad_points_kernel without its direction part: the 512 x 64 xyz weights staged once per workgroup
+//                            (128 KB of LDS, the same image), `contract` on slots 0 and 4 into two 32x32 accumulators, the Embedding
+//                            derivative with the forward's range reduction (sincos_rev_comp below), the half-wave shuffle, ONE 16-byte store per point:
+//                            g_xyz (P, 4) = [gx, gy, gz, 0].  Lanes of points >= P read the last real row and store nothing.
+//   point_grad_wsum_kernel   one wave per ray: sum_s w[r, s] g_xyz[r, s] in fp64 (the products are exact there), lane-strided, then the
+//                            butterfly of ray_grad_reduce_kernel; one rounding to fp32 -> g_sum (n_rays, 4) = [sum, 0].
+namespace snrg {
+
+constexpr int LDS_FLOATS_XYZ = 512 * 64;
+
+// sincos_rev (sn_device.h) with the rounding error of its one inexact step carried along.  The forward's range reduction is exact up
+// to t = fr + tl, whose rounding (2^-25 rev, 2e-7 rad) is an ABSOLUTE error of the angle: harmless for the embedded value, but a
+// derivative factor cos(2^k x) or sin(2^k x) that sits near one of its zeros would carry it as a RELATIVE error of any size, and a
+// per-point gradient -- unlike a sum over a ray's samples -- has nothing to hide it behind.  TwoSum keeps the lost part te and adds it
+// back after the quadrant is removed (r is exact and small exactly where it matters): both factors are then accurate relative to
+// their own magnitude.  Same reduction, same quadrant, same kernels; the value differs from sincos_rev's by at most that 2e-7.
+SN_DEV void sincos_rev_comp(Rev2 p, float scale, float& s, float& c) {
+  float th = p.hi * scale;                    // exact
+  float tl = p.lo * scale;                    // exact
+  float fr = th - __builtin_rintf(th);        // exact, in [-0.5, 0.5]
+  float t = fr + tl;                          // rounded ...
+  float bb = t - fr;
+  float te = (fr - (t - bb)) + (tl - bb);     // ... and what the rounding lost (TwoSum: exact)
+  float k = __builtin_rintf(t * 4.0f);        // quadrant -2..2
+  float r = __builtin_fmaf(k, -0.25f, t) + te;   // the fma is exact: |r| <= 1/8 rev
+  float a = r * 6.2831853071795864769f;       // radians, |a| <= pi/4
+  float a2 = a * a;
+  float sp = __builtin_fmaf(a2, -1.9515295891e-4f, 8.3321608736e-3f);
+  sp = __builtin_fmaf(sp, a2, -1.6666654611e-1f);
+  float sn = __builtin_fmaf(sp * a2, a, a);
+  float cp = __builtin_fmaf(a2, 2.443315711809948e-5f, -1.388731625493765e-3f);
+  cp = __builtin_fmaf(cp, a2, 4.166664568298827e-2f);
+  float cs = __builtin_fmaf(cp * a2, a2, __builtin_fmaf(a2, -0.5f, 1.0f));
+  int q = (int)k & 3;                          // two's complement: -1 -> 3, -2 -> 2
+  float s1 = (q & 1) ? cs : sn;
+  float c1 = (q & 1) ? sn : cs;
+  s = (q & 2) ? -s1 : s1;
+  c = ((q + 1) & 2) ? -c1 : c1;
+}
+
+template <int ROW>
+__global__ void __launch_bounds__(WAVES * 64)
+point_grad_kernel(const float* __restrict__ w1, const float* __restrict__ w5, const char* __restrict__ g_acts, long slot_rows,
+                  const float* __restrict__ rays, const float* __restrict__ z_vals, long n_points, int S,
+                  float* __restrict__ g_xyz) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* lds_x = reinterpret_cast<float*>(smem);         // source 0 = W1 (k 0..255), source 1 = W5[:, 0:63]
+  constexpr int NQ = RowTraits<ROW>::NQ;
+  constexpr long RB = RowTraits<ROW>::ROW_BYTES;
+
+  // ---- stage the weights once per workgroup: the LDS image of ray_grad_points_kernel's xyz part
+  for (int idx = threadIdx.x; idx < 512 * 64; idx += WAVES * 64) {
+    const int k = idx >> 6, f = idx & 63, tile = f >> 5, i = f & 31;
+    const int col = xyz_col(row_half(i), 16 * tile + row_reg(i));
+    float w = 0.0f;
+    if (col >= 0) w = k < 256 ? w1[k * 63 + col] : w5[(k - 256) * 319 + col];
+    lds_x[(k >> 8) * (256 * 64) + lds_pos<NQ>(k & 255, tile, 2, i)] = w;
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int h = lane >> 5;
+  const long n_tiles = (n_points + PTS_WG - 1) / PTS_WG;
+  for (long tile_i = blockIdx.x; tile_i < n_tiles; tile_i += gridDim.x) {
+    const long p = tile_i * PTS_WG + wave * 32 + (lane & 31);
+    const long pl = p < n_points ? p : n_points - 1;     // rows >= n_points are never read; such a lane stores nothing
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    contract<ROW, 2, 256>(g_acts + (0 * slot_rows + pl) * RB, lds_x, lane, acc);
+    contract<ROW, 2, 256>(g_acts + (4 * slot_rows + pl) * RB, lds_x + 256 * 64, lane, acc);
+
+    // ---- embedding derivative (nerf.py:36-41) at xyz = o + d*z with separate roundings, the point the forward embedded
+    const float* rp = rays + (pl / S) * 8;
+    const float zz = z_vals[pl];
+    const float x = __fadd_rn(rp[0], __fmul_rn(rp[3], zz)), y = __fadd_rn(rp[1], __fmul_rn(rp[4], zz)),
+                z = __fadd_rn(rp[2], __fmul_rn(rp[5], zz));
+    float gx[3] = {0.0f, 0.0f, 0.0f};
+    const Rev2 px = to_revolutions(x), py = to_revolutions(y), pz = to_revolutions(z);
+    const float hs = h ? 32.0f : 1.0f;                // bands 5..9 on the upper lane half
+#pragma unroll
+    for (int pp = 0; pp < 15; ++pp) {
+      const Rev2 pc = (pp % 3 == 0) ? px : (pp % 3 == 1) ? py : pz;
+      const float scale = hs * (float)(1 << (pp / 3));
+      float s, c;
+      sincos_rev_comp(pc, scale, s, c);
+      const float g_sin = acc[(2 * pp) >> 4][(2 * pp) & 15], g_cos = acc[(2 * pp + 1) >> 4][(2 * pp + 1) & 15];
+      gx[pp % 3] += scale * (c * g_sin - s * g_cos);
+    }
+    if (h) gx[2] += acc[1][14];                        // identity columns: x, y on the lower half, z on the upper
+    else { gx[0] += acc[1][14]; gx[1] += acc[1][15]; }
+    // the two lane halves hold disjoint bands of the same point
+#pragma unroll
+    for (int a = 0; a < 3; ++a) gx[a] += __shfl_xor(gx[a], 32, 64);
+    if (h == 0 && p < n_points) {
+      f32x4 out;
+      out[0] = gx[0]; out[1] = gx[1]; out[2] = gx[2]; out[3] = 0.0f;
+      *reinterpret_cast<f32x4*>(g_xyz + p * 4) = out;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256)
+point_grad_wsum_kernel(const float* __restrict__ g_xyz, const float* __restrict__ weights, long n_rays, int S,
+                       float* __restrict__ g_sum) {
+  const int lane = threadIdx.x & 63;
+  const long ray = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ray >= n_rays) return;
+  double a[3] = {0, 0, 0};
+  const f32x4* src = reinterpret_cast<const f32x4*>(g_xyz + ray * (long)S * 4);
+  const float* w = weights + ray * (long)S;
+  for (int s = lane; s < S; s += 64) {
+    const f32x4 g = src[s];
+    const double ws = (double)w[s];
+    a[0] += ws * (double)g[0]; a[1] += ws * (double)g[1]; a[2] += ws * (double)g[2];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) a[k] = wave_sum(a[k]);
+  if (lane == 0) {
+    f32x4 out;
+    out[0] = (float)a[0]; out[1] = (float)a[1]; out[2] = (float)a[2]; out[3] = 0.0f;
+    *reinterpret_cast<f32x4*>(g_sum + ray * 4) = out;
+  }
+}
+
+}  // namespace snrg
+
+// layout: 0 = fp32 rows, 1 = bf16 rows, 2 = (hi, lo) pairs of the bf16x3 state
+extern "C" int sn_point_grads_launch(const float* w1, const float* w5, int layout, const void* g_acts, long slot_rows,
+                                     const float* rays, const float* z_vals, long n_rays, int n_samples, float* g_xyz,
+                                     hipStream_t stream) {
+  using namespace snrg;
+  if (n_rays <= 0) return 0;
+  const long n_points = n_rays * (long)n_samples;
+  const long tiles = (n_points + PTS_WG - 1) / PTS_WG;
+  const unsigned grid = snh::persistent_grid(tiles);
+  constexpr size_t lds = LDS_FLOATS_XYZ * sizeof(float);
+  const char* G = reinterpret_cast<const char*>(g_acts);
+#define SN_PG(R)                                                                                                   \
+  {                                                                                                                \
+    SN_ENSURE_DYN_LDS((point_grad_kernel<R>), lds);                                                                \
+    hipLaunchKernelGGL((point_grad_kernel<R>), dim3(grid), dim3(WAVES * 64), lds, stream, w1, w5, G, slot_rows,    \
+                       rays, z_vals, n_points, n_samples, g_xyz);                                                  \
+  }
+  if (layout == 0) SN_PG(ROW_F32)
+  else if (layout == 1) SN_PG(ROW_BF16)
+  else SN_PG(ROW_X3)
+#undef SN_PG
+  return (int)hipGetLastError();
+}
+
+extern "C" int sn_point_grads_wsum_launch(const float* g_xyz, const float* weights, long n_rays, int n_samples, float* g_sum,
+                                          hipStream_t stream) {
+  if (n_rays <= 0) return 0;
+  const long ray_blocks = (n_rays + 3) / 4;
+  if (ray_blocks > 0x7fffffffL) return SN_E_TOOLARGE;
+  hipLaunchKernelGGL(snrg::point_grad_wsum_kernel, dim3((unsigned)ray_blocks), dim3(256), 0, stream, g_xyz, weights, n_rays,
+                     n_samples, g_sum);
+  return (int)hipGetLastError();
+}
