@@ -536,6 +536,35 @@ long sn_select_landed_workspace_bytes(long n);
 int sn_select_landed(const unsigned char* mask, long n, const float* u, long m, int* idx, int* n_landed, void* workspace,
                      void* stream);
 
+/* ---- the one-image training sampler (additive within ABI 5; sinnerf_amd/sampler.py): the device form of the two rejection loops of
+ * datasets/blender_ray_patch_1image_rot3d.py:451-460 and :486-499, and of the strided slices of :456-457, :491-497 and :523-528.
+ *
+ * A loop that redraws a uniform window origin until the window has content accepts an origin uniform over the origins WITH content:
+ * that is "the floor(u N)-th set element" (sn_select_landed) of the map sn_valid_windows writes.
+ *   mask (H, W) uint8, non-zero = set.  A window at origin (x0, y0) -- x the column -- covers the pixels (y0 + j stride_y,
+ *   x0 + i stride_x), 0 <= j < patch_h, 0 <= i < patch_w.  Candidates: 0 <= x0 < nx, 0 <= y0 < ny.
+ *   valid (ny, nx) uint8: 1 where any pixel of the window is set, else 0.  n_valid (one int32, may be NULL) receives the sum of valid.
+ *   Two passes, rows then columns (patch_w + patch_h reads per origin), integer sums: the same bits on every call.
+ *   workspace: the bytes the query returns for (H, nx); it need not be initialised.
+ * SN_E_BADARG: a null required pointer; H, W, a stride, a patch size, nx or ny <= 0; a candidate window that leaves the frame, that is
+ * nx > W - (patch_w - 1) stride_x or ny > H - (patch_h - 1) stride_y.  SN_E_TOOLARGE: H W >= 2^31.                                 */
+long sn_valid_windows_workspace_bytes(int H, int nx);
+int sn_valid_windows(const unsigned char* mask, int H, int W, int stride_x, int stride_y, int patch_w, int patch_h, int nx, int ny,
+                     unsigned char* valid, int* n_valid, void* workspace, void* stream);
+
+/* One strided window out of n_src (1..SN_GATHER_MAX_SOURCES) full-frame CHANNEL-LAST arrays of 32-bit words, in one launch.
+ *   src[k] (H, W, channels[k]) and dst[k] are DEVICE pointers; the arrays src, dst and channels themselves are HOST arrays of n_src
+ *   entries, read during the call and handed to the kernel by value.  dst[k] is written as (patch_h, patch_w, channels[k]), or planar
+ *   (channels[k], patch_h, patch_w) where bit k of planar_mask is set; it must not overlap a source.  Words are copied bit for bit.
+ *   origin: two int32 in DEVICE memory, (x0, y0), read by the kernel -- typically formed from the index sn_select_landed wrote.  Each is
+ *   clamped into [0, W - (patch_w - 1) stride_x) resp. [0, H - (patch_h - 1) stride_y), so that an origin of -1 (nothing valid) reads the
+ *   window at 0 and no value of the two words can make the kernel read outside a source.
+ * SN_E_BADARG: a null pointer (an entry of src or dst included); n_src outside 1..8; a bit of planar_mask at or above n_src; H, W, a
+ * stride, a patch size or a channel count <= 0; a window that fits at no origin.  SN_E_TOOLARGE: H W channels[k] >= 2^31.      */
+#define SN_GATHER_MAX_SOURCES 8
+int sn_gather_windows(const void* const* src, void* const* dst, const int* channels, int n_src, unsigned planar_mask, int H, int W,
+                      const int* origin, int stride_x, int stride_y, int patch_w, int patch_h, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,10 @@ SIGNATURES = {
                                c_vp, c_vp, c_vp, c_vp]),
     "sn_select_landed_workspace_bytes": (_long, [_long]),
     "sn_select_landed": (_int, [c_vp, _long, c_fp, _long, c_vp, c_vp, c_vp, c_vp]),
+    "sn_valid_windows_workspace_bytes": (_long, [_int, _int]),
+    "sn_valid_windows": (_int, [c_vp, _int, _int, _int, _int, _int, _int, _int, _int, c_vp, c_vp, c_vp, c_vp]),
+    "sn_gather_windows": (_int, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(_int), _int, ctypes.c_uint, _int, _int, c_vp,
+                                 _int, _int, _int, _int, c_vp]),
     "sn_composite_backward": (_int, [c_fp, c_fp, c_fp, c_fp, _float, _long, _int, _int, c_fp, c_fp, c_fp, c_fp, c_vp]),
     "sn_ray_grads_workspace_bytes": (_long, [_long, _int]),
     "sn_ray_grads": (_int, [c_fp, c_fp, c_fp, _int, c_vp, _long, c_fp, c_fp, _long, _int, c_vp, c_fp, c_vp]),

@@ -446,6 +446,42 @@ int sn_select_landed(const unsigned char* mask, long n, const float* u, long m, 
   return sn_select_landed_launch(mask, n, u, m, idx, n_landed, workspace, (hipStream_t)stream);
 }
 
+namespace {
+// a (patch_w, patch_h) window of strides (stride_x, stride_y): how many origins keep it inside the frame, per axis; <= 0: none
+long origins_that_fit(int extent, int patch, int stride) { return (long)extent - (long)(patch - 1) * stride; }
+}  // namespace
+
+long sn_valid_windows_workspace_bytes(int H, int nx) {
+  if (H <= 0 || nx <= 0) return SN_E_BADARG;
+  if ((long)H * nx >= (1l << 31)) return SN_E_TOOLARGE;
+  return sn_valid_windows_workspace_bytes_impl(H, nx);
+}
+
+int sn_valid_windows(const unsigned char* mask, int H, int W, int stride_x, int stride_y, int patch_w, int patch_h, int nx, int ny,
+                     unsigned char* valid, int* n_valid, void* workspace, void* stream) {
+  if (!mask || !valid || !workspace) return SN_E_BADARG;
+  if (const int refused = check_frame(H, W)) return refused;
+  if (stride_x <= 0 || stride_y <= 0 || patch_w <= 0 || patch_h <= 0 || nx <= 0 || ny <= 0) return SN_E_BADARG;
+  if (nx > origins_that_fit(W, patch_w, stride_x) || ny > origins_that_fit(H, patch_h, stride_y)) return SN_E_BADARG;
+  return sn_valid_windows_launch(mask, H, W, stride_x, stride_y, patch_w, patch_h, nx, ny, valid, n_valid, workspace,
+                                 (hipStream_t)stream);
+}
+
+int sn_gather_windows(const void* const* src, void* const* dst, const int* channels, int n_src, unsigned planar_mask, int H, int W,
+                      const int* origin, int stride_x, int stride_y, int patch_w, int patch_h, void* stream) {
+  if (!src || !dst || !channels || !origin || n_src <= 0 || n_src > SN_GATHER_MAX_SOURCES) return SN_E_BADARG;
+  if (const int refused = check_frame(H, W)) return refused;
+  if (stride_x <= 0 || stride_y <= 0 || patch_w <= 0 || patch_h <= 0) return SN_E_BADARG;
+  if (origins_that_fit(W, patch_w, stride_x) < 1 || origins_that_fit(H, patch_h, stride_y) < 1) return SN_E_BADARG;
+  if (n_src < 32 && (planar_mask >> n_src) != 0) return SN_E_BADARG;
+  for (int k = 0; k < n_src; ++k) {
+    if (!src[k] || !dst[k] || channels[k] <= 0) return SN_E_BADARG;
+    if ((long)H * W * channels[k] >= (1l << 31)) return SN_E_TOOLARGE;
+  }
+  return sn_gather_windows_launch(src, dst, channels, n_src, planar_mask, H, W, origin, stride_x, stride_y, patch_w, patch_h,
+                                  (hipStream_t)stream);
+}
+
 int sn_dw_gemm(const void* tasks, int n_tasks, void* stream) {
   if (!tasks || n_tasks < 0) return SN_E_BADARG;
   return sn_dw_launch(tasks, n_tasks, (hipStream_t)stream);

@@ -210,4 +210,10 @@ int sn_forward_warp_launch(const float* ref_depth, const float* data, int H, int
 long sn_select_landed_workspace_bytes_impl(long n);
 int sn_select_landed_launch(const unsigned char* mask, long n, const float* u, long m, int* idx, int* n_landed, void* workspace,
                             hipStream_t stream);
+// the one-image sampler: window origins with content, strided windows out of full frames (sn_sampler.hip)
+long sn_valid_windows_workspace_bytes_impl(int H, int nx);
+int sn_valid_windows_launch(const unsigned char* mask, int H, int W, int stride_x, int stride_y, int patch_w, int patch_h, int nx, int ny,
+                            unsigned char* valid, int* n_valid, void* workspace, hipStream_t stream);
+int sn_gather_windows_launch(const void* const* src, void* const* dst, const int* channels, int n_src, unsigned planar_mask, int H, int W,
+                             const int* origin, int stride_x, int stride_y, int patch_w, int patch_h, hipStream_t stream);
 }  // extern "C"

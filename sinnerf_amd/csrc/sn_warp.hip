@@ -2,7 +2,8 @@
 // pixels that landed, gfx950 (the prose of both entries: include/sinnerf_hip.h):
 //
 //   warp_prepare_kernel    clears the keys; thread 0 of block 0 forms M = (src_proj ref_proj^-1)[:3, :] in fp64 (Gauss-Jordan)
-//   warp_scatter_kernel    one thread per SOURCE pixel: project in fp64, clamp, one 32-bit atomicMax or 64-bit atomicMin on the target's key
+//   warp_scatter_kernel    one thread per SOURCE pixel: project in fp64, clamp; per wave ONE 32-bit atomicMax or 64-bit atomicMin on the key
+//                          of each distinct target (the lanes that share a target combine first)
 //   warp_resolve_kernel    one thread per WINDOW pixel: decode the key, copy the winner's data row, recompute its depth
 //   select_count_kernel / select_scan_kernel / select_pick_kernel      the k-th set element of a mask: block sums, their scan by one
 //                          block, a binary search over blocks and a ballot / popcount walk inside the block -- integer sums, no atomics
@@ -65,20 +66,45 @@ __global__ void __launch_bounds__(256)
 warp_scatter_kernel(const float* __restrict__ ref_depth, const double* __restrict__ M, int H, int W, double eps, int mode,
                     unsigned long long* __restrict__ keys) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)H * W) return;
-  const int y = (int)(i / W), x = (int)(i - (long)y * W);
-  double p0, p1, p2;
-  project(M, x, y, (double)ref_depth[i], p0, p1, p2);
-  const double xs = p0 / (p2 + eps), ys = p1 / (p2 + eps);
-  if (xs != xs || ys != ys) return;                                   // NaN: the source pixel is dropped
-  // clamped in floating point, so +-inf and anything beyond int range end on a border before the conversion
-  const int tx = (int)fmin(fmax(floor(xs), 0.0), (double)(W - 1)), ty = (int)fmin(fmax(floor(ys), 0.0), (double)(H - 1));
-  const long t = (long)ty * W + tx;
-  if (mode == 0) {
-    atomicMax(reinterpret_cast<int*>(keys) + t, (int)i);
-  } else {
+  const int lane = threadIdx.x & 63;
+  bool live = i < (long)H * W;                                        // no early return: the whole wave walks the loop below together
+  long t = -1;
+  unsigned long long key = EMPTY64;
+  if (live) {
+    const int y = (int)(i / W), x = (int)(i - (long)y * W);
+    double p0, p1, p2;
+    project(M, x, y, (double)ref_depth[i], p0, p1, p2);
+    const double xs = p0 / (p2 + eps), ys = p1 / (p2 + eps);
+    live = !(xs != xs || ys != ys);                                   // NaN: the source pixel is dropped
+    // clamped in floating point, so +-inf and anything beyond int range end on a border before the conversion
+    const int tx = (int)fmin(fmax(floor(xs), 0.0), (double)(W - 1)), ty = (int)fmin(fmax(floor(ys), 0.0), (double)(H - 1));
+    t = (long)ty * W + tx;
     const float df = (float)p2 + 0.0f;                                // -0.0 -> +0.0: equal depths tie on the index
-    atomicMin(keys + t, ((unsigned long long)ordered_bits(df) << 32) | (unsigned long long)(unsigned)i);
+    key = ((unsigned long long)ordered_bits(df) << 32) | (unsigned long long)(unsigned)i;
+  }
+  // One atomic per DISTINCT target of the wave, not per lane.  The zero-depth background of a blender frame sends tens of thousands of
+  // source pixels to one target, and that many atomics on one address take their turns (1.08 of the 1.44 ms of a 400 x 400 sampler
+  // draw before this loop).  max and min are associative, so the key ends where the per-lane atomics left it.
+  unsigned long long todo = __ballot(live);
+  while (todo != 0ull) {                                              // wave-uniform: every lane sees the same ballot
+    const int lead = __ffsll((long long)todo) - 1;
+    const long t_lead = __shfl(t, lead, 64);
+    const bool mine = live && t == t_lead;
+    const unsigned long long group = __ballot(mine);
+    if (mode == 0) {                                                  // the largest index of the group is its highest lane's
+      if (lane == 63 - __clzll((long long)group)) atomicMax(reinterpret_cast<int*>(keys) + t, (int)i);
+    } else if ((group & (group - 1ull)) == 0ull) {                    // a group of one
+      if (mine) atomicMin(keys + t, key);
+    } else {
+      unsigned long long k = mine ? key : EMPTY64;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(k, o, 64);
+        k = other < k ? other : k;
+      }
+      if (lane == lead) atomicMin(keys + t, k);
+    }
+    todo &= ~group;
   }
 }
 

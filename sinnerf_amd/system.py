@@ -461,6 +461,57 @@ class SinNeRFSystem(nn.Module):
         g.replay()
         return out
 
+    def train_step_sampled(self, sampler, graph=False):
+        """``train_step`` on a batch drawn on the device: ``batch = sampler.draw()`` (``sinnerf_amd.sampler.OneImageSampler``: what the
+        reference's DataLoader workers build per sample on the CPU), then zero -> forward -> loss -> backward and the optimiser's
+        exchange step.  No part of the step waits for the host.
+
+        ``graph=True``: the draw is INSIDE the captured region, in front of the step; every replay draws fresh randoms (torch's
+        generators advance their offset per replay; a sampler's own generator is registered with the graph).  Warm-up and invalidation as
+        for ``train_step(graph=True)``; the cache key adds the sampler's identity and shapes.  Returns the step's dict with the batch
+        under ``"batch"`` (with ``graph=True``: static tensors, overwritten by the next replay)."""
+        self._ensure_flat_optimizer()
+        if graph:
+            out = self._graphed_sampled_step(sampler)
+        else:
+            batch = sampler.draw()
+            out = dict(self._zero_forward_backward(batch), batch=batch)
+        self.optimizer.step()
+        return out
+
+    def _graphed_sampled_step(self, sampler):
+        hp = self.hparams
+        key = ("sampled", id(sampler), sampler.signature(),
+               self.optimizer.flat.data_ptr() if isinstance(self.optimizer, FlatOptimizer) else None,
+               self._flat.flat.data_ptr() if self._flat is not None else None,
+               hp.N_samples, hp.N_importance, hp.use_disp, hp.perturb, hp.noise_std, hp.chunk, hp.depth_weight,
+               hp.compute_dtype, self.white_back, self.training, hp.patch_loss, hp.depth_smooth_weight, hp.proj_weight,
+               hp.dataset_name)
+        cache = self.__dict__.setdefault("_step_graphs", {})     # shared with _graphed_step: dropped with it when the buffers move
+        hit = cache.get(key)
+        if hit is None:
+            if not isinstance(self.optimizer, FlatOptimizer):
+                raise RuntimeError("train_step_sampled(graph=True) needs the flat optimiser (parameters on a ROCm device)")
+            cur = torch.cuda.current_stream()
+            side = torch.cuda.Stream()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):        # the warm-up of _graphed_step, the draw included
+                for _ in range(2):
+                    self._zero_forward_backward(sampler.draw())
+            cur.wait_stream(side)
+            for m in self.models:                # the re-pack of the weight blobs belongs to the captured step (_graphed_step)
+                m.invalidate_packed()
+            g = torch.cuda.CUDAGraph()
+            if sampler.generator is not None:
+                g.register_generator_state(sampler.generator)
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                batch = sampler.draw()
+                out = dict(self._zero_forward_backward(batch), batch=batch)
+            hit = cache[key] = (g, sampler, out)                 # the sampler is kept: its id stays its own while the entry lives
+        g, _, out = hit
+        g.replay()
+        return out
+
     def replica_checksum(self):
         """fp64 sum and sum of squares of the flat parameter buffer: equal on every rank iff the replicas are identical
         (what the bench's multi-GPU training leg asserts after a few steps)."""

@@ -27,7 +27,8 @@ def _pose44(c2w):
     """(3, 4) or (4, 4) -> (4, 4) fp64 with the last row 0 0 0 1"""
     if tuple(c2w.shape) not in ((3, 4), (4, 4)):
         raise RuntimeError(f"a pose must be (3, 4) or (4, 4), got {tuple(c2w.shape)}")
-    bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=torch.float64, device=c2w.device)
+    bottom = torch.zeros((1, 4), dtype=torch.float64, device=c2w.device)      # built by fills: a literal is copied from the host, which a
+    bottom[:, 3:] = 1.0                                                       # stream under capture refuses (so it does `bottom[0, 3] = 1.0`)
     return torch.cat([c2w[:3].double(), bottom], 0)
 
 
@@ -42,7 +43,8 @@ def extrinsics_from_c2w(c2w, convention="opengl"):
     p = _pose44(c2w)
     R, T = p[:3, :3], p[:3, 3:]
     if convention == "opengl":
-        flip = torch.tensor([1.0, -1.0, -1.0], dtype=torch.float64, device=p.device)[:, None]
+        flip = torch.ones((3, 1), dtype=torch.float64, device=p.device)
+        flip[1:] = -1.0
         Ri = flip * R.t()
     else:                                                   # rows of the inverse: cross products of the columns over the determinant
         c0, c1, c2 = R[:, 0], R[:, 1], R[:, 2]
@@ -73,7 +75,7 @@ def projection_matrix(intrinsics, extrinsics):
     """``[K E[:3]; 0 0 0 1]`` (4, 4) fp64 on the device"""
     P = torch.zeros((4, 4), dtype=torch.float64, device=intrinsics.device)
     P[:3] = intrinsics.double() @ extrinsics.double()[:3]
-    P[3, 3] = 1.0
+    P[3:, 3:] = 1.0                                         # a slice: `P[3, 3] = 1.0` is refused by a stream under capture
     return P
 
 
@@ -221,3 +223,25 @@ def unseen_view_batch(ref_view, ref_depth, K, ref_c2w, side_c2w, near, far, wind
             "depth_proj": depth_full[at] * valid,
             "side_coord": torch.stack([rows, cols]) if ph == pw else (rows, cols),
             "n_landed": n_landed}
+
+
+def unseen_view_full(ref_view, ref_depth, K, ref_c2w, side_c2w, near, far, collide="last", *, focal, eps=0.0, center=None,
+                     convention="opengl", ndc_near=None, ref_proj=None):
+    """The FULL frame of the unseen view, for a caller that picks its window on the device afterwards (``sinnerf_amd.sampler``): the
+    reference view and its depth warped into ``side_c2w`` by ONE ``sn_forward_warp`` (``blender_ray_patch_1image_rot3d.py:481-484``) and
+    the rays of ``side_c2w`` by one ``get_rays`` (``:476-479``).  Arguments as for ``unseen_view_batch``, without a window and ``u_proj``;
+    ``ref_proj``: the (4, 4) fp64 projection matrix of the reference pose where the caller keeps it (it does not change between draws).
+
+    Returns a dict: ``out`` (H, W, C), ``depth`` (H, W), ``mask`` (H, W) uint8 -- 1 where a pixel landed -- and ``rays`` (H * W, 8).
+    No value moves to the host and nothing is built from host literals, so the call can be captured in a graph."""
+    data, depth = _prepare("unseen_view_full", ref_view, ref_depth, collide)
+    _need_cuda("unseen_view_full", K, ref_c2w, side_c2w, ref_proj)
+    if data is None:
+        raise RuntimeError("unseen_view_full: ref_view is required")
+    H, W = depth.shape
+    ref_P = projection_matrix(K, extrinsics_from_c2w(ref_c2w, convention)) if ref_proj is None else ref_proj.detach().double()
+    src_P = projection_matrix(K, extrinsics_from_c2w(side_c2w, convention))
+    new, new_depth, mask, _, _ = _warp(data, depth, ref_P.contiguous(), src_P.contiguous(), COLLIDE[collide], eps, None)
+    focal, center = (v.detach() if torch.is_tensor(v) else v for v in (focal, center))       # labels: no gradient
+    rays = get_rays(H, W, focal, side_c2w[:3].detach().float(), near, far, None, center=center, convention=convention, ndc_near=ndc_near)
+    return {"out": new.reshape(H, W, -1), "depth": new_depth.reshape(H, W), "mask": mask.reshape(H, W), "rays": rays}
