@@ -497,6 +497,29 @@ long sn_depth_smoothness_workspace_bytes(void);
 int sn_depth_smoothness(const float* idepth, const float* image, int B, int H, int W, int C, float* g_idepth, float* g_image,
                         void* workspace, float* out, void* stream);
 
+/* ---- regularisers on the distribution of the compositing weights along a ray, forward + gradients in two launches (additive within
+ * ABI 5): the distortion loss of Mip-NeRF 360 (eq. 15) and the ray entropy of InfoNeRF (eqs. 5-7).  Per ray of S = n_samples samples,
+ * weights w_i, depths z_i (ascending, ties allowed), near = rays[r, 6], far = rays[r, 7]:
+ *   inv  = far > near ? 1 / (far - near) : 0;  s_i = (z_i - near) inv;
+ *   m_i  = (s_i + s_{i+1}) / 2 for i < S - 1, m_{S-1} = s_{S-1};  d_i = s_{i+1} - s_i for i < S - 1, d_{S-1} = 0 (the compositor's
+ *          1e10 last delta is not a length);
+ *   dist = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i;
+ *   o = sum_i w_i, q = o + 1e-10, p_i = w_i / q, H = -sum_i p_i log(p_i + 1e-10); mask = o > ent_threshold (a constant for the
+ *   gradient); ent = mask ? H : 0.
+ *   Both are means over ALL n_rays rays (the entropy as mean(mask H), not a mean over the masked rays);
+ *   total = w_dist mean(dist) + w_ent mean(ent).
+ *   weights, z_vals (n_rays, n_samples), rays (n_rays, 8): DEVICE fp32.  z_vals, near and far are data: no gradient.
+ *   g_weights (n_rays, n_samples): d total / d weights = (w_dist ddist/dw + w_ent mask dH/dw) / n_rays, written, not accumulated; NULL =
+ *   not wanted.  per_ray (n_rays, 2) = (dist, ent) of each ray; NULL = not wanted.
+ *   out[4] = mean dist, mean ent, total, number of rays with the mask set.
+ *   workspace: the bytes the query returns for n_rays, DEVICE scratch.  fp64 arithmetic on the fp32 inputs, one rounding per output,
+ *   sums in a fixed order without atomics: two calls give the same bits.  No host read-back, no allocation: capturable.
+ * SN_E_BADARG: a null required pointer.  SN_E_BADSHAPE: n_samples outside 1..1024.  SN_E_TOOLARGE: more than 2^33 - 4 rays.
+ * n_rays <= 0 launches nothing, sets out to {0, 0, 0, 0} on the stream and returns 0.                                              */
+long sn_ray_regularizers_workspace_bytes(long n_rays);
+int sn_ray_regularizers(const float* weights, const float* z_vals, const float* rays, long n_rays, int n_samples, float w_dist,
+                        float w_ent, float ent_threshold, float* g_weights, float* per_ray, void* workspace, float* out, void* stream);
+
 /* ---- the forward warp of the reference view and its depth into the unseen view (additive within ABI 5): project_with_depth +
  * forward_warp of datasets/blender_ray_patch_1image_rot3d.py:103-150 (called per training sample, :481-484),
  * blender_ray_patch_1image_proj.py:93-138 (with depth_mask, :135-137), llff_ray_patch_1image_proj.py:117-166 (painter's loop :161-165)

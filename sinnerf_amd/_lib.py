@@ -71,6 +71,8 @@ SIGNATURES = {
     "sn_patch_loss": (_int, [c_fp, c_fp, c_fp, _int, _int, _int, _int, _int, _int, _float, _float, c_fp, c_fp, c_vp, c_fp, c_vp]),
     "sn_depth_smoothness_workspace_bytes": (_long, []),
     "sn_depth_smoothness": (_int, [c_fp, c_fp, _int, _int, _int, _int, c_fp, c_fp, c_vp, c_fp, c_vp]),
+    "sn_ray_regularizers_workspace_bytes": (_long, [_long]),
+    "sn_ray_regularizers": (_int, [c_fp, c_fp, c_fp, _long, _int, _float, _float, _float, c_fp, c_fp, c_vp, c_fp, c_vp]),
     "sn_forward_warp_workspace_bytes": (_long, [_int, _int]),
     "sn_forward_warp": (_int, [c_fp, c_fp, _int, _int, _int, c_vp, c_vp, _double, _int, _int, _int, _int, _int, _int, _int, c_fp, c_fp,
                                c_vp, c_vp, c_vp, c_vp]),

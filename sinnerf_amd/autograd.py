@@ -273,9 +273,9 @@ class _CompositeFn(torch.autograd.Function):
 
 
 def render_rays_autograd(models, rays, N_samples, use_disp, perturb, noise_std, N_importance, white_back, test_time,
-                         detach_coarse):
+                         detach_coarse, keep=None):
     """Differentiable ``render_rays`` (called by ``rendering.render_rays`` when a model parameter or ``rays`` requires grad).
-    Same stage order and RNG consumption as ``rendering._forward_core``."""
+    Same stage order and RNG consumption as ``rendering._forward_core``.  ``keep`` (dict): receives the depths of the passes."""
     from . import rendering as R
     dev = rays.device
     n = rays.shape[0]
@@ -337,6 +337,8 @@ def render_rays_autograd(models, rays, N_samples, use_disp, perturb, noise_std, 
                             "as in the reference: rendering.py:331)")
         result.update(rgb_fine=result["rgb_coarse"], depth_fine=result["depth_coarse"],
                       opacity_fine=result["opacity_coarse"])
+    if keep is not None:
+        R._keep_depths(keep, z_vals, z_all if N_importance > 0 else None, dev, N_samples, N_importance)
     return result
 
 

@@ -410,6 +410,17 @@ int sn_depth_smoothness(const float* idepth, const float* image, int B, int H, i
   return sn_depth_smoothness_launch(idepth, image, B, H, W, C, g_idepth, g_image, workspace, out, (hipStream_t)stream);
 }
 
+// ---- the regularisers on a ray's compositing weights (sn_ray_reg.hip)
+long sn_ray_regularizers_workspace_bytes(long n_rays) { return sn_ray_regularizers_workspace_bytes_impl(n_rays); }
+
+int sn_ray_regularizers(const float* weights, const float* z_vals, const float* rays, long n_rays, int n_samples, float w_dist,
+                        float w_ent, float ent_threshold, float* g_weights, float* per_ray, void* workspace, float* out, void* stream) {
+  if (!weights || !z_vals || !rays || !workspace || !out) return SN_E_BADARG;
+  if (n_samples < 1 || n_samples > 1024) return SN_E_BADSHAPE;
+  return sn_ray_regularizers_launch(weights, z_vals, rays, n_rays, n_samples, w_dist, w_ent, ent_threshold, g_weights, per_ray,
+                                    workspace, out, (hipStream_t)stream);
+}
+
 // ---- the unseen-view forward warp (sn_warp.hip): every refusal below returns before a launch
 namespace {
 int check_frame(int H, int W) {

@@ -202,6 +202,11 @@ int sn_patch_loss_launch(const float* coarse, const float* fine, const float* ta
 long sn_depth_smoothness_workspace_bytes_impl();
 int sn_depth_smoothness_launch(const float* idepth, const float* image, int B, int H, int W, int C, float* g_idepth, float* g_image,
                                void* workspace, float* out, hipStream_t stream);
+// the regularisers on a ray's compositing weights (sn_ray_reg.hip)
+long sn_ray_regularizers_workspace_bytes_impl(long n_rays);
+int sn_ray_regularizers_launch(const float* weights, const float* z_vals, const float* rays, long n_rays, int n_samples, float w_dist,
+                               float w_ent, float ent_threshold, float* g_weights, float* per_ray, void* workspace, float* out,
+                               hipStream_t stream);
 // the unseen-view forward warp and the draw among the landed pixels (sn_warp.hip)
 long sn_forward_warp_workspace_bytes_impl(int H, int W);
 int sn_forward_warp_launch(const float* ref_depth, const float* data, int H, int W, int C, const double* ref_proj, const double* src_proj,

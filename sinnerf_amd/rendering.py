@@ -121,6 +121,14 @@ def _empty_result(dev, N_samples, N_importance, test_time):
     return res
 
 
+def _keep_depths(keep, z_coarse, z_fine, dev, N_samples, N_importance):
+    """``render_rays(keep=...)``: the depths of the two passes, detached (an empty batch: empty tensors of the right widths)"""
+    e = lambda width: torch.empty((0, width), dtype=torch.float32, device=dev)
+    keep["z_vals_coarse"] = z_coarse.detach() if z_coarse is not None else e(N_samples)
+    if N_importance > 0:
+        keep["z_vals_fine"] = z_fine.detach() if z_fine is not None else e(N_samples + N_importance)
+
+
 def _forward_core(models, rays, N_samples, use_disp, perturb, noise_std, N_importance, white_back, test_time,
                   flags=0, keep=None):
     """No-grad forward of the whole path.  ``keep`` (dict) receives the intermediates the backward needs."""
@@ -180,6 +188,7 @@ def render_rays(models,
                 test_time=False,
                 detach_coarse=False,
                 noisy_coarse=True,
+                keep=None,
                 ):
     """Render rays -- drop-in for reference ``models/rendering.py:126-335`` (same arguments, same dict).
 
@@ -192,6 +201,11 @@ def render_rays(models,
     and directions (``rays[:, 0:6]``; build the rays with ``ray_utils.get_rays`` to reach ``c2w``).  Limitation: near / far
     (``rays[:, 6:8]``) are treated as constants -- their gradient columns are zero, where the reference would differentiate the
     coarse depths through them (no reference call site does).  ``compute_dtype="fp16"`` is inference only.
+
+    ``keep`` (a dict, after the reference's 13 arguments) receives the depths the passes used, detached: ``z_vals_coarse``
+    (N_rays, N_samples) and, when ``N_importance > 0``, ``z_vals_fine`` (N_rays, N_samples + N_importance) -- what
+    ``regularizers.ray_regularizers`` pairs with ``opacity_coarse`` / ``opacity_fine``.  The result dict, the RNG consumption and every
+    bit of the results are the same with and without it.
     """
     if not isinstance(rays, torch.Tensor) or not rays.is_cuda:
         raise RuntimeError("sinnerf_amd.render_rays: rays must be a CUDA/ROCm tensor (there is no CPU fallback)")
@@ -216,10 +230,14 @@ def render_rays(models,
         if needs_grad and rays.shape[0] > 0:
             from .autograd import render_rays_autograd
             return render_rays_autograd(models, rays, N_samples, use_disp, perturb, noise_std, N_importance,
-                                        white_back, test_time, detach_coarse)
+                                        white_back, test_time, detach_coarse, keep=keep)
         with torch.no_grad():
-            return _forward_core(models, rays, N_samples, use_disp, perturb, noise_std, N_importance, white_back,
-                                 test_time)
+            passes = {} if keep is not None else None
+            result = _forward_core(models, rays, N_samples, use_disp, perturb, noise_std, N_importance, white_back,
+                                   test_time, keep=passes)
+            if keep is not None:
+                _keep_depths(keep, passes.get("z_coarse"), passes.get("z_fine"), rays.device, N_samples, N_importance)
+            return result
 
 
 @torch.no_grad()

@@ -23,6 +23,7 @@ from .nerf import Embedding, NeRF
 from .optim import FlatAdam, FlatOptimizer, FlatSGD, GradualWarmupScheduler, get_optimizer, get_scheduler
 from .parallel import all_reduce_mean_grads, broadcast_parameters
 from .losses import inverse_depth_smoothness_loss, loss_dict, psnr, render_loss      # noqa: F401  (psnr re-exported: metrics.py:14-15)
+from .regularizers import ray_regularizers
 from .rendering import render_rays
 
 DEFAULT_HPARAMS = dict(N_samples=64, N_importance=64, use_disp=False, perturb=1.0, noise_std=1.0, chunk=32 * 1024,
@@ -37,7 +38,10 @@ DEFAULT_HPARAMS = dict(N_samples=64, N_importance=64, use_disp=False, perturb=1.
                        patch_loss="mse", depth_smooth_weight=0.0, proj_weight=1.0, dataset_name=None,
                        # the reference's optimiser and schedule flags with its defaults (opt.py:45-71; sinnerf_amd/optim.py builds them)
                        optimizer="adam", momentum=0.9, lr_scheduler="steplr", num_epochs=80, poly_exp=0.9, warmup_multiplier=1.0,
-                       warmup_epochs=0)
+                       warmup_epochs=0,
+                       # regularisers on the compositing weights of the unseen-view render (sinnerf_amd/regularizers.py; not in the
+                       # reference): the distortion loss of Mip-NeRF 360 and the ray entropy of InfoNeRF.  The defaults add no term
+                       distortion_weight=0.0, entropy_weight=0.0, entropy_threshold=0.1)
 
 
 
@@ -133,17 +137,26 @@ class SinNeRFSystem(nn.Module):
         return {"loss": loss_d * self.hparams.dis_weight, "log": {"train/loss_d": loss_d.detach()}}
 
     # ---- sinnerf.py:171-193 -------------------------------------------------------------------------------------
-    def forward(self, rays):
+    def forward(self, rays, keep=None):
+        """``keep`` (a dict): receives the sample depths of the passes, as ``render_rays(keep=...)`` hands them out, joined over the
+        chunks like the results"""
         B = rays.shape[0]
-        results = defaultdict(list)
+        results, kept = defaultdict(list), defaultdict(list)
         hp = self.hparams
         for i in range(0, B, hp.chunk):
+            chunk_keep = {} if keep is not None else None
             chunk_res = render_rays(self.models, self.embeddings, rays[i:i + hp.chunk], hp.N_samples, hp.use_disp,
-                                    hp.perturb, hp.noise_std, hp.N_importance, hp.chunk, self.white_back)
+                                    hp.perturb, hp.noise_std, hp.N_importance, hp.chunk, self.white_back, keep=chunk_keep)
             for k, v in chunk_res.items():
                 results[k].append(v)
+            if keep is not None:
+                for k, v in chunk_keep.items():
+                    kept[k].append(v)
         # one chunk (every training batch): hand the tensors on -- torch.cat of a single tensor is a device copy per key
-        return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in results.items()}
+        join = lambda d: {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in d.items()}
+        if keep is not None:
+            keep.update(join(kept))
+        return join(results)
 
     # ---- sinnerf.py:202-210 + utils/__init__.py:11-57 -----------------------------------------------------------
     def configure_optimizers(self):
@@ -234,6 +247,10 @@ class SinNeRFSystem(nn.Module):
         * ``'warp_patch_depth'``: ``proj_weight * depth_weight`` x SmoothL1 of the side depths over its positive pixels (:399-406,
           504-505), zero when there is none -- decided on the device, no host sync;
         * ``depth_smooth_weight > 0``: the four ``inverse_depth_smoothness_loss`` terms (:370-373, 395-398, 509).
+
+        Not in the reference: with ``distortion_weight > 0`` or ``entropy_weight > 0``, ``ray_regularizers`` on the compositing weights
+        of the unseen-view render -- the fine pass, and the coarse pass when its weights carry a gradient.  ``results_side`` then holds
+        the depths of its passes under the private keys ``_z_vals_fine`` / ``_z_vals_coarse`` (``_training_step_patches`` puts them there).
         """
         hp = self.hparams
         wd = hp.depth_weight
@@ -285,6 +302,23 @@ class SinNeRFSystem(nn.Module):
                     l_sm = term if l_sm is None else l_sm + term
             loss = loss + hp.depth_smooth_weight * l_sm
             log["train/loss_depth_smooth"] = l_sm.detach()
+        if hp.distortion_weight > 0 or hp.entropy_weight > 0:
+            if "_z_vals_fine" not in results_side and "_z_vals_coarse" not in results_side:
+                raise RuntimeError("distortion_weight / entropy_weight > 0 need the depths of the side render: render it with "
+                                   "forward(rays, keep=d) and pass them as results_side['_z_vals_fine'] / ['_z_vals_coarse']")
+            rays_side = batch["rays_side"].reshape(-1, 8)
+            passes = [("opacity_fine", "_z_vals_fine" if "_z_vals_fine" in results_side else "_z_vals_coarse")]
+            if "_z_vals_fine" in results_side and results_side["opacity_coarse"].requires_grad:
+                passes.append(("opacity_coarse", "_z_vals_coarse"))
+            l_reg = l_dist = l_ent = None
+            for k_w, k_z in passes:
+                term, st = ray_regularizers(results_side[k_w], results_side[k_z], rays_side, hp.distortion_weight, hp.entropy_weight,
+                                            hp.entropy_threshold)
+                l_reg = term if l_reg is None else l_reg + term
+                l_dist = st["distortion"] if l_dist is None else l_dist + st["distortion"]
+                l_ent = st["entropy"] if l_ent is None else l_ent + st["entropy"]
+            loss = loss + l_reg
+            log["train/loss_distortion"], log["train/loss_ray_entropy"] = l_dist, l_ent
         l_side = self.side_loss(results_side, batch)
         if l_side is not None:
             loss = loss + l_side
@@ -296,7 +330,13 @@ class SinNeRFSystem(nn.Module):
         r8 = lambda k: batch[k].reshape(-1, 8)
         results = self(r8("rays"))                                              # sinnerf.py:304
         results_full = self(r8("rays_full"))                                    # :305
-        results_side = self(r8("rays_side"))                                    # :306
+        hp = self.hparams
+        if hp.distortion_weight > 0 or hp.entropy_weight > 0:                   # the side render with its depths, for patch_losses
+            kept = {}
+            results_side = self(r8("rays_side"), keep=kept)
+            results_side.update({"_" + k: v for k, v in kept.items()})
+        else:
+            results_side = self(r8("rays_side"))                                # :306
         results_proj = self(r8("rays_proj"))                                    # :307
         loss, log = self.patch_losses(results, results_full, results_side, results_proj, batch)
         return {"loss": loss, "progress_bar": {"train_psnr": log["train/psnr"]}, "log": log}
@@ -434,7 +474,7 @@ class SinNeRFSystem(nn.Module):
                self._flat.flat.data_ptr() if self._flat is not None else None,
                hp.N_samples, hp.N_importance, hp.use_disp, hp.perturb, hp.noise_std, hp.chunk, hp.depth_weight,
                hp.compute_dtype, self.white_back, self.training, hp.patch_loss, hp.depth_smooth_weight, hp.proj_weight,
-               hp.dataset_name)
+               hp.dataset_name, hp.distortion_weight, hp.entropy_weight, hp.entropy_threshold)
         cache = self.__dict__.setdefault("_step_graphs", {})
         hit = cache.get(key)
         if hit is None:
@@ -486,7 +526,7 @@ class SinNeRFSystem(nn.Module):
                self._flat.flat.data_ptr() if self._flat is not None else None,
                hp.N_samples, hp.N_importance, hp.use_disp, hp.perturb, hp.noise_std, hp.chunk, hp.depth_weight,
                hp.compute_dtype, self.white_back, self.training, hp.patch_loss, hp.depth_smooth_weight, hp.proj_weight,
-               hp.dataset_name)
+               hp.dataset_name, hp.distortion_weight, hp.entropy_weight, hp.entropy_threshold)
         cache = self.__dict__.setdefault("_step_graphs", {})     # shared with _graphed_step: dropped with it when the buffers move
         hit = cache.get(key)
         if hit is None:
