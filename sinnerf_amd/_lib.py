@@ -137,6 +137,15 @@ def check(code, what):
         raise SinnerfHipError(f"{what} failed: [{code}] {msg.decode() if msg else '?'}")
 
 
+def workspace(nbytes, what, device):
+    """the uint8 scratch tensor of a ``*_workspace_bytes`` answer; a negative answer is an error code and raises through check()"""
+    import torch
+    nbytes = int(nbytes)
+    if nbytes < 0:
+        check(nbytes, what)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def ptr(t):
     """device pointer of a contiguous torch tensor (or None)."""
     if t is None:

@@ -78,10 +78,7 @@ def _weight_grads(model, acts, emb, G, needs):
     dev = acts.device
     code = _state_code(model, acts, emb)
     rows = acts.shape[1]
-    nbytes = _lib.lib.sn_weight_grads_workspace_bytes(rows, code)
-    if nbytes < 0:
-        _lib.check(int(nbytes), "sn_weight_grads_workspace_bytes")
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(_lib.lib.sn_weight_grads_workspace_bytes(rows, code), "sn_weight_grads_workspace_bytes", dev)
     raws = model.raw_tensors()
     sink = _sink_of(model, raws, needs)
     if sink is not None:
@@ -108,10 +105,7 @@ def _ray_grads(model, G, rows, rays, z_vals):
     raws = model.raw_tensors()
     w1, w5, wdir = (raws[i].detach().contiguous().float() for i in (0, 8, 18))     # xyz_encoding_1 / _5 / dir_encoding weights
     code = _state_code(model, G) & ~_lib.SN_DTYPE_EMB_BF16
-    nbytes = _lib.lib.sn_ray_grads_workspace_bytes(n, s)
-    if nbytes < 0:
-        _lib.check(int(nbytes), "sn_ray_grads_workspace_bytes")
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=G.device)
+    ws = _lib.workspace(_lib.lib.sn_ray_grads_workspace_bytes(n, s), "sn_ray_grads_workspace_bytes", G.device)
     g_rays = torch.empty((n, 8), dtype=torch.float32, device=G.device)
     _lib.check(_lib.lib.sn_ray_grads(_lib.ptr(w1), _lib.ptr(w5), _lib.ptr(wdir), code, _lib.ptr(G), rows, _lib.ptr(rays), _lib.ptr(z_vals),
                                      n, s, _lib.ptr(ws), _lib.ptr(g_rays), _lib.stream_ptr()), "sn_ray_grads")

@@ -53,6 +53,18 @@ bool holds_whole_tiles(long slot_rows, long n_points, int base) {
   const long tile = tile_rows(base);
   return slot_rows >= (n_points + tile - 1) / tile * tile;
 }
+// the state of the weight-gradient entries is read in whole 16-row steps
+bool bad_slot_rows(long slot_rows) { return slot_rows < 16 || slot_rows % 16 != 0; }
+// the layout sn_mlp_backward_chain(base) left g_acts in for the ray / point gradients: 0 = fp32 rows, 1 = bf16 rows, 2 = x3 state
+int g_acts_layout(int base) { return base == SN_DTYPE_BF16_STATE ? 1 : base == SN_DTYPE_BF16X3 ? 2 : 0; }
+// a (patch_w, patch_h) window of strides (stride_x, stride_y) at (x0, y0) in an H x W frame, possibly empty: the part of its check
+// that is SN_E_BADARG, and the part that is SN_E_BADSHAPE (the window leaves the frame)
+bool window_badarg(int H, int W, int stride_x, int stride_y, int patch_w, int patch_h) {
+  return H < 1 || W < 1 || stride_x < 1 || stride_y < 1 || patch_w < 0 || patch_h < 0;
+}
+bool window_badshape(int H, int W, int x0, int y0, int stride_x, int stride_y, int patch_w, int patch_h) {
+  return x0 < 0 || y0 < 0 || (patch_w > 0 && x0 + (patch_w - 1) * stride_x >= W) || (patch_h > 0 && y0 + (patch_h - 1) * stride_y >= H);
+}
 bool packable(int dtype) { Dtype d; return parse_dtype(dtype, 0, PACKABLE, &d); }
 // sn_weight_grads and its two queries: SN_DTYPE_EMB_BF16 is the only bit, refused where the kernels cannot read that form (sn_launch.h)
 int parse_dw_dtype(int dtype, Dtype* d) {
@@ -322,9 +334,8 @@ int sn_mlp_backward_chain(const void* blob_bwd, int dtype, const float* acts, co
 
 int sn_generate_rays(const float* c2w, int H, int W, float focal, float near, float far, int x0, int y0, int stride_x,
                      int stride_y, int patch_w, int patch_h, float* rays, void* stream) {
-  if (!c2w || !rays || H < 1 || W < 1 || stride_x < 1 || stride_y < 1 || patch_w < 0 || patch_h < 0) return SN_E_BADARG;
-  if (x0 < 0 || y0 < 0 || (patch_w > 0 && x0 + (patch_w - 1) * stride_x >= W) || (patch_h > 0 && y0 + (patch_h - 1) * stride_y >= H))
-    return SN_E_BADSHAPE;
+  if (!c2w || !rays || window_badarg(H, W, stride_x, stride_y, patch_w, patch_h)) return SN_E_BADARG;
+  if (window_badshape(H, W, x0, y0, stride_x, stride_y, patch_w, patch_h)) return SN_E_BADSHAPE;
   return sn_generate_rays_launch(c2w, H, W, focal, near, far, x0, y0, stride_x, stride_y, patch_w, patch_h, rays,
                                  (hipStream_t)stream);
 }
@@ -499,7 +510,7 @@ int sn_dw_gemm(const void* tasks, int n_tasks, void* stream) {
 }
 
 long sn_weight_grads_workspace_bytes(long slot_rows, int dtype) {
-  if (slot_rows < 16 || slot_rows % 16 != 0) return SN_E_BADSHAPE;
+  if (bad_slot_rows(slot_rows)) return SN_E_BADSHAPE;
   Dtype d;
   if (const int refused = parse_dw_dtype(dtype, &d)) return refused;
   return sn_weight_grads_workspace_bytes_impl(slot_rows, d.base, d.bits);
@@ -507,7 +518,7 @@ long sn_weight_grads_workspace_bytes(long slot_rows, int dtype) {
 
 int sn_weight_grads_plan(long slot_rows, int dtype, int32_t* out_host, int max_probs) {
   // the checks of sn_weight_grads_workspace_bytes, in its order
-  if (slot_rows < 16 || slot_rows % 16 != 0) return SN_E_BADSHAPE;
+  if (bad_slot_rows(slot_rows)) return SN_E_BADSHAPE;
   Dtype d;
   if (const int refused = parse_dw_dtype(dtype, &d)) return refused;
   if (max_probs < 0 || (max_probs > 0 && !out_host)) return SN_E_BADARG;
@@ -518,7 +529,7 @@ int sn_weight_grads_plan(long slot_rows, int dtype, int32_t* out_host, int max_p
 int sn_weight_grads(const void* acts, const float* emb, const void* g_acts, long slot_rows, int dtype, void* workspace,
                     float* const* grads, int accumulate, void* stream) {
   if (!acts || !emb || !g_acts || !workspace || !grads) return SN_E_BADARG;
-  if (slot_rows < 16 || slot_rows % 16 != 0) return SN_E_BADSHAPE;
+  if (bad_slot_rows(slot_rows)) return SN_E_BADSHAPE;
   Dtype d;
   if (const int refused = parse_dw_dtype(dtype, &d)) return refused;
   return sn_weight_grads_launch(acts, emb, g_acts, slot_rows, d.base, d.bits, workspace, grads, accumulate ? 1 : 0, (hipStream_t)stream);
@@ -554,8 +565,7 @@ int sn_ray_grads(const float* w1, const float* w5, const float* wdir, int dtype,
   // the layout sn_mlp_backward_chain(dtype) left g_acts in; no flag bits: the heads and the kernel generation do not change it
   Dtype d;
   if (!parse_dtype(dtype, 0, TRAINABLE, &d)) return SN_E_UNSUPPORTED;
-  const int layout = d.base == SN_DTYPE_BF16_STATE ? 1 : d.base == SN_DTYPE_BF16X3 ? 2 : 0;      // fp32 rows / bf16 rows / x3 state
-  return sn_ray_grads_launch(w1, w5, wdir, layout, g_acts, slot_rows, rays, z_vals, n_rays, n_samples, workspace, g_rays,
+  return sn_ray_grads_launch(w1, w5, wdir, g_acts_layout(d.base), g_acts, slot_rows, rays, z_vals, n_rays, n_samples, workspace, g_rays,
                              (hipStream_t)stream);
 }
 
@@ -567,8 +577,7 @@ int sn_point_grads(const float* w1, const float* w5, int dtype, const void* g_ac
   // the layout sn_mlp_backward_chain(dtype) left g_acts in, as for sn_ray_grads: no flag bits
   Dtype d;
   if (!parse_dtype(dtype, 0, TRAINABLE, &d)) return SN_E_UNSUPPORTED;
-  const int layout = d.base == SN_DTYPE_BF16_STATE ? 1 : d.base == SN_DTYPE_BF16X3 ? 2 : 0;      // fp32 rows / bf16 rows / x3 pairs
-  return sn_point_grads_launch(w1, w5, layout, g_acts, slot_rows, rays, z_vals, n_rays, n_samples, g_xyz, (hipStream_t)stream);
+  return sn_point_grads_launch(w1, w5, g_acts_layout(d.base), g_acts, slot_rows, rays, z_vals, n_rays, n_samples, g_xyz, (hipStream_t)stream);
 }
 
 int sn_point_grads_wsum(const float* g_xyz, const float* weights, long n_rays, int n_samples, float* g_sum, void* stream) {
@@ -581,10 +590,8 @@ long sn_generate_rays_backward_workspace_bytes(void) { return sn_generate_rays_b
 
 int sn_generate_rays_backward(const float* g_rays, int H, int W, float focal, int x0, int y0, int stride_x, int stride_y,
                               int patch_w, int patch_h, void* workspace, float* g_c2w, void* stream) {
-  if (!g_rays || !workspace || !g_c2w || H < 1 || W < 1 || stride_x < 1 || stride_y < 1 || patch_w < 0 || patch_h < 0)
-    return SN_E_BADARG;
-  if (x0 < 0 || y0 < 0 || (patch_w > 0 && x0 + (patch_w - 1) * stride_x >= W) || (patch_h > 0 && y0 + (patch_h - 1) * stride_y >= H))
-    return SN_E_BADSHAPE;
+  if (!g_rays || !workspace || !g_c2w || window_badarg(H, W, stride_x, stride_y, patch_w, patch_h)) return SN_E_BADARG;
+  if (window_badshape(H, W, x0, y0, stride_x, stride_y, patch_w, patch_h)) return SN_E_BADSHAPE;
   return sn_generate_rays_backward_launch(g_rays, H, W, focal, x0, y0, stride_x, stride_y, patch_w, patch_h, workspace, g_c2w,
                                           (hipStream_t)stream);
 }
@@ -597,11 +604,10 @@ float ndc_scale(int size, float focal) { return (float)(-1.0 / ((double)size / (
 
 int check_camera(int H, int W, float fx, float fy, int convention, int ndc, float ndc_focal, int x0, int y0, int stride_x, int stride_y,
                  int patch_w, int patch_h) {
-  if (H < 1 || W < 1 || stride_x < 1 || stride_y < 1 || patch_w < 0 || patch_h < 0) return SN_E_BADARG;
+  if (window_badarg(H, W, stride_x, stride_y, patch_w, patch_h)) return SN_E_BADARG;
   if ((convention != 0 && convention != 1) || (ndc != 0 && ndc != 1)) return SN_E_BADARG;
   if (!positive_finite(fx) || !positive_finite(fy) || !positive_finite(ndc_focal)) return SN_E_BADARG;
-  if (x0 < 0 || y0 < 0 || (patch_w > 0 && x0 + (patch_w - 1) * stride_x >= W) || (patch_h > 0 && y0 + (patch_h - 1) * stride_y >= H))
-    return SN_E_BADSHAPE;
+  if (window_badshape(H, W, x0, y0, stride_x, stride_y, patch_w, patch_h)) return SN_E_BADSHAPE;
   return 0;
 }
 }  // namespace

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include "../../include/sinnerf_hip.h"
 #include "sn_device.h"
@@ -43,6 +44,39 @@ inline unsigned persistent_grid(long tiles) {
   const int n_cu = cu_count();
   return (unsigned)(tiles < n_cu ? tiles : n_cu);
 }
+
+// grid of a one-wave-per-ray kernel: blocks of 256 threads = four rays each.  Returns 0, or SN_E_TOOLARGE beyond what a grid holds.
+inline long ray_blocks(long n_rays) { return (n_rays + 3) / 4; }
+inline int ray_grid(long n_rays, dim3* grid) {
+  const long blocks = ray_blocks(n_rays);
+  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
+  *grid = dim3((unsigned)blocks);
+  return 0;
+}
+
+// ... and its samples per lane C = ceil(n_samples / 64): lane l owns the samples [l C, (l + 1) C).  0: outside the 1..16 the kernels
+// are instantiated for (the entry names the error).  for_samples_per_lane calls f(std::integral_constant<int, C>) for that C.
+inline int samples_per_lane(int n_samples) {
+  const int C = (n_samples + 63) / 64;
+  return C >= 1 && C <= 16 ? C : 0;
+}
+template <typename F>
+inline void for_samples_per_lane(int C, F&& f) {
+  switch (C) {
+#define SN_C_(CC) case CC: f(std::integral_constant<int, CC>{}); break;
+    SN_C_(1) SN_C_(2) SN_C_(3) SN_C_(4) SN_C_(5) SN_C_(6) SN_C_(7) SN_C_(8)
+    SN_C_(9) SN_C_(10) SN_C_(11) SN_C_(12) SN_C_(13) SN_C_(14) SN_C_(15) SN_C_(16)
+#undef SN_C_
+  }
+}
+
+// blocks of 256 threads of a grid-stride kernel over n > 0 elements, at most cap; the _min1 form for a launch that must run on
+// empty input too (its finisher still writes zeros)
+inline unsigned stride_grid(long n, long cap) {
+  const long blocks = (n + 255) / 256;
+  return (unsigned)(blocks > cap ? cap : blocks);
+}
+inline unsigned stride_grid_min1(long n, long cap) { return n > 0 ? stride_grid(n, cap) : 1u; }
 
 // Kernels that deal their work units dynamically (sn_mlp_fwd_f32g.hip) draw tickets from one word of a per-device array of UNIT_WORDS
 // words that the kernel's translation unit owns.  unit_word(stream) = the index of the stream's word on the current device: launches on
@@ -173,9 +207,9 @@ int sn_ndc_rays_launch(const float* rays_in, long n_rays, float ax, float ay, fl
 int sn_ndc_rays_backward_launch(const float* rays_in, const float* g_rays_out, long n_rays, float ax, float ay, float ndc_near,
                                 float* g_rays_in, const float* focal, int H, int W, void* workspace, float* g_focal,
                                 hipStream_t stream);
+// the optimisers over the flat buffers (sn_optim.hip); the scalars of SGD / RAdam / Ranger arrive in double and are rounded to fp32 once.
 int sn_adam_step_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                         float wd, int step, hipStream_t stream);
-// the other optimisers of the reference over the same flat buffers (sn_optim.hip); the scalars arrive in double and are rounded to fp32 once.
 // sn_radam_step_launch: slow == nullptr is RAdam, otherwise Ranger (lookahead into slow when sync != 0)
 int sn_sgd_step_launch(float* p, const float* g, float* buf, long n, double lr, double momentum, double wd, hipStream_t stream);
 int sn_radam_step_launch(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, double decay,

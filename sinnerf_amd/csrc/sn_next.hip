@@ -3,8 +3,6 @@
 //   generate_rays_kernel   datasets/ray_utils.py:86-133 (get_ray_directions + get_rays) and the [o, d, near, far] packing
 //                          of the datasets (blender_ray_patch_1image_rot3d.py:201-211, strided patches :487-498):
 //                          rays are produced ON the GPU from (c2w, focal) -- no (H*W, 8) host array, no H2D copy.
-//   adam_kernel            utils/__init__.py:19-21 (torch.optim.Adam, eps=1e-8) over ONE flat parameter/gradient buffer
-//                          (the buffer the single RCCL all-reduce runs on): one elementwise launch per step.
 //   rays_bwd_*_kernel      the backward of generate_rays_kernel w.r.t. c2w (pose gradients): 12 deterministic sums over the rays.
 //   generate_rays_cam_kernel / rays_cam_bwd_partials_kernel / ndc_rays_kernel / ndc_rays_bwd_kernel
 //                          the two above for the reference's other cameras: separate fx, fy, a principal point and the OpenCV
@@ -20,6 +18,7 @@
 // All are HBM-bound elementwise kernels: coalesced, 16-byte accesses where the layout allows.
 #include "sn_device.h"
 #include "sn_launch.h"
+#include "sn_wave.h"
 
 namespace snx {
 
@@ -51,26 +50,8 @@ generate_rays_kernel(const float* __restrict__ c2w, int H, int W, float focal, f
   }
 }
 
-// torch.optim.Adam (amsgrad=False, maximize=False), weight_decay folded in L2 style like torch:
-//   g += wd*p ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
-__global__ void __launch_bounds__(256)
-adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
-            float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-  const float step_size = lr / bc1;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float gi = g[i];
-    const float pi = p[i];
-    if (wd != 0.0f) gi = gi + wd * pi;
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
-  }
-}
-
 // ---- losses on the rendered rays ---------------------------------------------------------------------------------
-// Deterministic two-phase reduction: every block accumulates its grid-stride share in double and writes 5 partials
+// Deterministic two-phase reduction (sn_wave.h): every block accumulates its grid-stride share in double and writes 5 partials
 // (sum (rgb_c-gt)^2, sum (rgb_f-gt)^2, sum sl1(depth_c-gt), sum sl1(depth_f-gt), number of depth elements counted);
 // the finish kernel re-reduces the <= LOSS_BLOCKS partials in index order in every block (so each block knows the
 // normalisers) and writes the gradients; block 0 writes the scalars.
@@ -79,15 +60,6 @@ constexpr int LOSS_BLOCKS = 256;
 SN_DEV bool depth_counted(const float* depth_gt, const unsigned char* mask, int mask_mode, long i) {
   // SL1Loss.forward: mask given -> it; mask None and useMask -> depth_gt > 0; useMask=False -> everything
   return mask_mode == 0 ? true : (mask_mode == 1 ? depth_gt[i] > 0.0f : mask[i] != 0);
-}
-SN_DEV double block_sum(double v, double* sh) {   // all 256 threads; result valid in every thread
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
 __global__ void __launch_bounds__(256)
@@ -112,11 +84,7 @@ loss_partials_kernel(const float* __restrict__ rgb_c, const float* __restrict__ 
       if (depth_f != nullptr) { const float d = fabsf(depth_f[i] - g); a[3] += (double)(d < 1.0f ? 0.5f * d * d : d - 0.5f); }
       a[4] += 1.0;
     }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const double v = block_sum(a[k], sh);
-    if (threadIdx.x == 0) partials[blockIdx.x * 5 + k] = v;
-  }
+  snwv::write_block_partials(a, sh, partials);
 }
 
 // out[8] = mse_coarse, mse_fine, sl1_coarse, sl1_fine, total = w_rgb (mse_c + mse_f) + w_depth (sl1_c + sl1_f),
@@ -130,11 +98,7 @@ loss_finish_kernel(const float* __restrict__ rgb_c, const float* __restrict__ rg
                    float* __restrict__ g_depth_f, float* __restrict__ out) {
   __shared__ double sh[4];
   double tot[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const double v = (int)threadIdx.x < n_partials ? partials[threadIdx.x * 5 + k] : 0.0;
-    tot[k] = block_sum(v, sh);
-  }
+  snwv::sum_partials(partials, n_partials, sh, tot);
   const double n_rgb = 3.0 * (double)n, n_d = tot[4];
   const float mse_c = rgb_c && rgb_gt ? (float)(tot[0] / n_rgb) : 0.0f, mse_f = rgb_f && rgb_gt ? (float)(tot[1] / n_rgb) : 0.0f;
   const float sl_c = depth_c && depth_gt ? (float)(tot[2] / n_d) : 0.0f, sl_f = depth_f && depth_gt ? (float)(tot[3] / n_d) : 0.0f;
@@ -192,22 +156,17 @@ rays_bwd_partials_kernel(const float* __restrict__ g_rays, int H, int W, float f
       a[4 * r + 0] += gd[r] * d0; a[4 * r + 1] += gd[r] * d1; a[4 * r + 2] += gd[r] * d2; a[4 * r + 3] += go[r];
     }
   }
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const double v = block_sum(a[k], sh);
-    if (threadIdx.x == 0) partials[blockIdx.x * 12 + k] = v;
-  }
+  snwv::write_block_partials(a, sh, partials);
 }
 
 __global__ void __launch_bounds__(256)
 rays_bwd_finish_kernel(const double* __restrict__ partials, int n_partials, float* __restrict__ g_c2w) {
   __shared__ double sh[4];
+  double tot[12];
+  snwv::sum_partials(partials, n_partials, sh, tot);
+  if (threadIdx.x != 0) return;
 #pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const double v = (int)threadIdx.x < n_partials ? partials[threadIdx.x * 12 + k] : 0.0;
-    const double t = block_sum(v, sh);
-    if (threadIdx.x == 0) g_c2w[k] = (float)t;
-  }
+  for (int k = 0; k < 12; ++k) g_c2w[k] = (float)tot[k];
 }
 
 // ---- the reference's other cameras: llff (get_ndc_rays, datasets/ray_utils.py:123-164) and dtu (get_ray_directions_dtu,
@@ -351,22 +310,19 @@ ndc_rays_bwd_kernel(const float* __restrict__ rays_in, const float* __restrict__
                     const float* __restrict__ focal, int H, int W, float* __restrict__ g_in, double* __restrict__ partials) {
   __shared__ double sh[4];
   if (FOCAL) camera_ndc_focal(cam, focal[0], H, W);
-  double g_ax = 0.0, g_ay = 0.0;
+  double g_a[NDC_SUMS] = {0.0, 0.0};             // g_ax, g_ay
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
     const float4* in = reinterpret_cast<const float4*>(rays_in + idx * 8);
     const float4* g = reinterpret_cast<const float4*>(g_out + idx * 8);
     const float4 lo = in[0], hi = in[1], glo = g[0], ghi = g[1];
     const float o[3] = {lo.x, lo.y, lo.z}, d[3] = {lo.w, hi.x, hi.y};
     float go[3] = {glo.x, glo.y, glo.z}, gd[3] = {glo.w, ghi.x, ghi.y};
-    if (FOCAL) ndc_scale_sums(cam, o, d, go, gd, g_ax, g_ay);
+    if (FOCAL) ndc_scale_sums(cam, o, d, go, gd, g_a[0], g_a[1]);
     ndc_map_adjoint(cam, o, d, go, gd);
     float4* out = reinterpret_cast<float4*>(g_in + idx * 8);
     out[0] = make_float4(go[0], go[1], go[2], gd[0]); out[1] = make_float4(gd[1], gd[2], 0.0f, 0.0f);
   }
-  if (FOCAL) {
-    const double vx = block_sum(g_ax, sh), vy = block_sum(g_ay, sh);
-    if (threadIdx.x == 0) { partials[blockIdx.x * NDC_SUMS + 0] = vx; partials[blockIdx.x * NDC_SUMS + 1] = vy; }
-  }
+  if (FOCAL) snwv::write_block_partials(g_a, sh, partials);
 }
 
 // rays_bwd_partials_kernel for any of the cameras: with ndc on, the upstream gradient of each ray first goes back through the
@@ -416,11 +372,7 @@ rays_cam_bwd_partials_kernel(const float* __restrict__ g_rays, const float* __re
       a[12] += gc0 * (-d0 / fx); a[13] += gc1 * (-d1 / fy); a[14] += gc0 * (-1.0 / fx); a[15] += gc1 * (-s / fy);
     }
   }
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const double v = block_sum(a[k], sh);
-    if (threadIdx.x == 0) partials[blockIdx.x * NS + k] = v;
-  }
+  snwv::write_block_partials(a, sh, partials);
 }
 
 // rays_bwd_finish_kernel for NS sums per block: the <= RAYS_BWD_BLOCKS partials added in index order, then
@@ -432,11 +384,7 @@ rays_intr_bwd_finish_kernel(const double* __restrict__ partials, int n_partials,
                             float* __restrict__ g_intr) {
   __shared__ double sh[4];
   double tot[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const double v = (int)threadIdx.x < n_partials ? partials[threadIdx.x * NS + k] : 0.0;
-    tot[k] = block_sum(v, sh);
-  }
+  snwv::sum_partials(partials, n_partials, sh, tot);
   if (threadIdx.x != 0) return;
   if constexpr (NS == CAM_SUMS) {
     if (g_c2w != nullptr) {
@@ -458,9 +406,7 @@ extern "C" int sn_generate_rays_launch(const float* c2w, int H, int W, float foc
                                        int sx, int sy, int pw, int ph, float* rays, hipStream_t stream) {
   const long total = (long)pw * ph;
   if (total <= 0) return 0;
-  long blocks = (total + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(snx::generate_rays_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, c2w, H, W, focal, near, far,
+  hipLaunchKernelGGL(snx::generate_rays_kernel, dim3(snh::stride_grid(total, 4096)), dim3(256), 0, stream, c2w, H, W, focal, near, far,
                      x0, y0, sx, sy, pw, ph, rays);
   return (int)hipGetLastError();
 }
@@ -470,11 +416,9 @@ extern "C" int sn_generate_rays_backward_launch(const float* g_rays, int H, int 
                                                 int pw, int ph, void* workspace, float* g_c2w, hipStream_t stream) {
   using namespace snx;
   const long total = (long)pw * ph;
-  long blocks = (total + 255) / 256;
-  if (blocks < 1) blocks = 1;                    // an empty window still writes its 12 zeros
-  if (blocks > RAYS_BWD_BLOCKS) blocks = RAYS_BWD_BLOCKS;
+  const unsigned blocks = snh::stride_grid_min1(total, RAYS_BWD_BLOCKS);       // an empty window still writes its 12 zeros
   double* partials = reinterpret_cast<double*>(workspace);
-  hipLaunchKernelGGL(rays_bwd_partials_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, H, W, focal, x0, y0, sx, sy,
+  hipLaunchKernelGGL(rays_bwd_partials_kernel, dim3(blocks), dim3(256), 0, stream, g_rays, H, W, focal, x0, y0, sx, sy,
                      pw, ph, partials);
   hipLaunchKernelGGL(rays_bwd_finish_kernel, dim3(1), dim3(256), 0, stream, partials, (int)blocks, g_c2w);
   return (int)hipGetLastError();
@@ -492,14 +436,13 @@ extern "C" int sn_generate_rays_cam_launch(const float* c2w, float fx, float fy,
   using namespace snx;
   const long total = (long)pw * ph;
   if (total <= 0) return 0;
-  long blocks = (total + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
+  const unsigned blocks = snh::stride_grid(total, 4096);
   const Camera cam = make_camera(fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near);
   const Window win{x0, y0, sx, sy, pw, ph};
   if (intr != nullptr)
-    hipLaunchKernelGGL(generate_rays_cam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, c2w, cam, intr, H, W, near, far, win, rays);
+    hipLaunchKernelGGL(generate_rays_cam_kernel<true>, dim3(blocks), dim3(256), 0, stream, c2w, cam, intr, H, W, near, far, win, rays);
   else
-    hipLaunchKernelGGL(generate_rays_cam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, c2w, cam, intr, H, W, near, far, win, rays);
+    hipLaunchKernelGGL(generate_rays_cam_kernel<false>, dim3(blocks), dim3(256), 0, stream, c2w, cam, intr, H, W, near, far, win, rays);
   return (int)hipGetLastError();
 }
 
@@ -511,19 +454,17 @@ extern "C" int sn_generate_rays_cam_backward_launch(const float* g_rays, const f
                                                     float* g_intr, hipStream_t stream) {
   using namespace snx;
   const long total = (long)pw * ph;
-  long blocks = (total + 255) / 256;
-  if (blocks < 1) blocks = 1;                    // an empty window still writes its zeros
-  if (blocks > RAYS_BWD_BLOCKS) blocks = RAYS_BWD_BLOCKS;
+  const unsigned blocks = snh::stride_grid_min1(total, RAYS_BWD_BLOCKS);       // an empty window still writes its zeros
   double* partials = reinterpret_cast<double*>(workspace);
   const Camera cam = make_camera(fx, fy, cx, cy, convention, ndc, ax, ay, ndc_near);
   const Window win{x0, y0, sx, sy, pw, ph};
   if (intr != nullptr) {
-    hipLaunchKernelGGL(rays_cam_bwd_partials_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, c2w, cam, intr, H, W, win,
+    hipLaunchKernelGGL(rays_cam_bwd_partials_kernel<true>, dim3(blocks), dim3(256), 0, stream, g_rays, c2w, cam, intr, H, W, win,
                        partials);
     hipLaunchKernelGGL(rays_intr_bwd_finish_kernel<CAM_SUMS>, dim3(1), dim3(256), 0, stream, partials, (int)blocks, -2.0 / (double)W,
                        -2.0 / (double)H, g_c2w, g_intr);
   } else {
-    hipLaunchKernelGGL(rays_cam_bwd_partials_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, g_rays, c2w, cam, intr, H, W, win,
+    hipLaunchKernelGGL(rays_cam_bwd_partials_kernel<false>, dim3(blocks), dim3(256), 0, stream, g_rays, c2w, cam, intr, H, W, win,
                        partials);
     hipLaunchKernelGGL(rays_bwd_finish_kernel, dim3(1), dim3(256), 0, stream, partials, (int)blocks, g_c2w);
   }
@@ -534,13 +475,12 @@ extern "C" int sn_ndc_rays_launch(const float* rays_in, long n_rays, float ax, f
                                   const float* focal, int H, int W, hipStream_t stream) {
   using namespace snx;
   if (n_rays <= 0) return 0;
-  long blocks = (n_rays + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
+  const unsigned blocks = snh::stride_grid(n_rays, 4096);
   const Camera cam = make_camera(1.0f, 1.0f, 0.0f, 0.0f, 0, 1, ax, ay, ndc_near);
   if (focal != nullptr)
-    hipLaunchKernelGGL(ndc_rays_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, n_rays, cam, focal, H, W, rays_out);
+    hipLaunchKernelGGL(ndc_rays_kernel<true>, dim3(blocks), dim3(256), 0, stream, rays_in, n_rays, cam, focal, H, W, rays_out);
   else
-    hipLaunchKernelGGL(ndc_rays_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, n_rays, cam, focal, H, W, rays_out);
+    hipLaunchKernelGGL(ndc_rays_kernel<false>, dim3(blocks), dim3(256), 0, stream, rays_in, n_rays, cam, focal, H, W, rays_out);
   return (int)hipGetLastError();
 }
 
@@ -550,32 +490,18 @@ extern "C" int sn_ndc_rays_backward_launch(const float* rays_in, const float* g_
                                            float* g_focal, hipStream_t stream) {
   using namespace snx;
   const Camera cam = make_camera(1.0f, 1.0f, 0.0f, 0.0f, 0, 1, ax, ay, ndc_near);
-  long blocks = (n_rays + 255) / 256;
   if (focal != nullptr) {
-    if (blocks < 1) blocks = 1;
-    if (blocks > RAYS_BWD_BLOCKS) blocks = RAYS_BWD_BLOCKS;
+    const unsigned blocks = snh::stride_grid_min1(n_rays, RAYS_BWD_BLOCKS);
     double* partials = reinterpret_cast<double*>(workspace);
-    hipLaunchKernelGGL(ndc_rays_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, g_rays_out, n_rays, cam, focal, H,
+    hipLaunchKernelGGL(ndc_rays_bwd_kernel<true>, dim3(blocks), dim3(256), 0, stream, rays_in, g_rays_out, n_rays, cam, focal, H,
                        W, g_rays_in, partials);
     hipLaunchKernelGGL(rays_intr_bwd_finish_kernel<NDC_SUMS>, dim3(1), dim3(256), 0, stream, partials, (int)blocks, -2.0 / (double)W,
                        -2.0 / (double)H, (float*)nullptr, g_focal);
     return (int)hipGetLastError();
   }
   if (n_rays <= 0) return 0;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(ndc_rays_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, rays_in, g_rays_out, n_rays, cam, focal, H, W,
+  hipLaunchKernelGGL(ndc_rays_bwd_kernel<false>, dim3(snh::stride_grid(n_rays, 4096)), dim3(256), 0, stream, rays_in, g_rays_out, n_rays, cam, focal, H, W,
                      g_rays_in, (double*)nullptr);
-  return (int)hipGetLastError();
-}
-
-extern "C" int sn_adam_step_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
-                                   float eps, float wd, int step, hipStream_t stream) {
-  if (n <= 0) return 0;
-  const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
-  long blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(snx::adam_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, n, lr, b1, b2, eps, wd,
-                     (float)bc1, (float)sqrt(bc2));
   return (int)hipGetLastError();
 }
 
@@ -585,13 +511,11 @@ extern "C" int sn_render_loss_launch(const float* rgb_c, const float* rgb_f, con
                                      long n, float w_rgb, float w_depth, float* g_rgb_c, float* g_rgb_f, float* g_depth_c,
                                      float* g_depth_f, void* workspace, float* out, hipStream_t stream) {
   using namespace snx;
-  long blocks = (3 * n + 255) / 256;
-  if (blocks < 1) blocks = 1;
-  if (blocks > LOSS_BLOCKS) blocks = LOSS_BLOCKS;
+  const unsigned blocks = snh::stride_grid_min1(3 * n, LOSS_BLOCKS);
   double* partials = reinterpret_cast<double*>(workspace);
-  hipLaunchKernelGGL(loss_partials_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, rgb_c, rgb_f, depth_c, depth_f,
+  hipLaunchKernelGGL(loss_partials_kernel, dim3(blocks), dim3(256), 0, stream, rgb_c, rgb_f, depth_c, depth_f,
                      rgb_gt, depth_gt, mask, mask_mode, n, partials);
-  hipLaunchKernelGGL(loss_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, rgb_c, rgb_f, depth_c, depth_f,
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(blocks), dim3(256), 0, stream, rgb_c, rgb_f, depth_c, depth_f,
                      rgb_gt, depth_gt, mask, mask_mode, n, w_rgb, w_depth, partials, (int)blocks, g_rgb_c, g_rgb_f,
                      g_depth_c, g_depth_f, out);
   return (int)hipGetLastError();

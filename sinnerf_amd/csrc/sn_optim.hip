@@ -1,7 +1,8 @@
-// sn_optim.hip -- the reference's other optimisers over ONE flat fp32 parameter / gradient buffer (the all-reduce buffer), gfx950:
+// sn_optim.hip -- the reference's optimisers over ONE flat fp32 parameter / gradient buffer (the all-reduce buffer), gfx950:
+//   adam_kernel     utils/__init__.py:19-21 (torch.optim.Adam, eps=1e-8); in namespace snx, the name the traces and profiles know it by
 //   sgd_kernel      utils/__init__.py:16-18 (torch.optim.SGD: momentum, dampening 0, no Nesterov, weight decay folded into the gradient)
 //   radam_kernel    utils/optimizers.py:62-104 (RAdam) and :393-437 (Ranger = the same moments and update + lookahead), the element-wise part
-// one launch per step, in place, like adam_kernel (sn_next.hip).  The per-step scalars -- N_sma, the rectified / degenerate step size, their
+// one launch per step, in place.  The per-step scalars of the last two -- N_sma, the rectified / degenerate step size, their
 // products with the learning rate, whether the lookahead fires -- are computed by the caller in double from the HOST step counter and
 // arrive rounded to fp32 once, as torch rounds a Python scalar; nothing is read back from the device.
 //
@@ -10,6 +11,28 @@
 // under -ffp-contract=off: one rounding per operation, in the reference's order.
 #include "sn_device.h"
 #include "sn_launch.h"
+
+namespace snx {
+
+// torch.optim.Adam (amsgrad=False, maximize=False), weight_decay folded in L2 style like torch:
+//   g += wd*p ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+__global__ void __launch_bounds__(256)
+adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+            float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+  const float step_size = lr / bc1;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float gi = g[i];
+    const float pi = p[i];
+    if (wd != 0.0f) gi = gi + wd * pi;
+    const float mi = b1 * m[i] + (1.0f - b1) * gi;
+    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = pi - step_size * (mi / denom);
+  }
+}
+
+}  // namespace snx
 
 namespace sno {
 
@@ -97,15 +120,18 @@ radam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restri
 inline bool aligned16(const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
 
 // grid-stride, 256 threads, at most 4096 blocks (adam_kernel's shape), counted in the units a thread handles
-inline unsigned grid_for(long n4, long n) {
-  const long units = n4 > 0 ? n4 : n;
-  long blocks = (units + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
+inline unsigned grid_for(long n4, long n) { return snh::stride_grid_min1(n4 > 0 ? n4 : n, 4096); }
 
 }  // namespace sno
+
+extern "C" int sn_adam_step_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
+                                   float eps, float wd, int step, hipStream_t stream) {
+  if (n <= 0) return 0;
+  const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
+  hipLaunchKernelGGL(snx::adam_kernel, dim3(snh::stride_grid(n, 4096)), dim3(256), 0, stream, p, g, m, v, n, lr, b1, b2, eps, wd,
+                     (float)bc1, (float)sqrt(bc2));
+  return (int)hipGetLastError();
+}
 
 extern "C" int sn_sgd_step_launch(float* p, const float* g, float* buf, long n, double lr, double momentum, double wd, hipStream_t stream) {
   using namespace sno;

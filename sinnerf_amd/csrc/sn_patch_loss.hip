@@ -10,9 +10,10 @@
 // no permute copy stands between the renderer and the loss.  Patches are 64 x 64 or 56 x 70: the cost is launches, not arithmetic, and
 // the arithmetic is spent on accuracy instead -- window sums, the SSIM quotient, its partial derivatives and the adjoint filter are fp64
 // (F(a a) - mu^2 cancels, and at a == b the three adjoint terms cancel each other); one rounding to fp32 where a value leaves.
-// Reductions as in sn_next.hip: per-block partials in double, re-reduced in index order -- deterministic, no atomics.
+// Reductions with the helpers of sn_wave.h: per-block partials in double, re-reduced in index order -- deterministic, no atomics.
 #include "sn_device.h"
 #include "sn_launch.h"
+#include "sn_wave.h"
 
 namespace snp {
 
@@ -22,16 +23,6 @@ constexpr int REG = TILE + 2 * MAX_R;            // the tile with its halo
 constexpr int FLAT_BLOCKS = 256;                 // grid cap of the grid-stride kernels (= partial records they write)
 
 struct Taps { double g[2 * MAX_R + 1]; };        // the normalised 1-D gaussian, formed on the host in double
-
-SN_DEV double block_sum(double v, double* sh) {   // all 256 threads; result valid in every thread
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 // index of torch's reflect padding for e in [-r, n - 1 + r], r < n; clamped so that no caller can leave the plane
 SN_DEV int reflect(int e, int n) {
@@ -110,11 +101,7 @@ ssim_stats_kernel(const float* __restrict__ coarse, const float* __restrict__ fi
     }
   }
   const double sums[3] = {acc_c, acc_f, acc_s};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double v = block_sum(sums[k], sh);
-    if (tid == 0) partials[(long)blockIdx.x * 3 + k] = v;
-  }
+  snwv::write_block_partials(sums, sh, partials);
 }
 
 // the MSE pair alone: the patch as a flat array of n elements
@@ -129,11 +116,7 @@ mse_partials_kernel(const float* __restrict__ coarse, const float* __restrict__ 
     if (fine != nullptr) { const float d = fine[i] - tg; acc_f += (double)(d * d); }
   }
   const double sums[3] = {acc_c, acc_f, 0.0};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double v = block_sum(sums[k], sh);
-    if (threadIdx.x == 0) partials[(long)blockIdx.x * 3 + k] = v;
-  }
+  snwv::write_block_partials(sums, sh, partials);
 }
 
 // the pre-images of pixel v under the reflect padding: the extended coordinates e in [-r, n - 1 + r] with reflect(e) == v
@@ -197,12 +180,7 @@ patch_grad_kernel(const float* __restrict__ coarse, const float* __restrict__ fi
     }
   if (blockIdx.x != 0) return;
   double tot[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    double v = 0.0;
-    for (int i = threadIdx.x; i < n_partials; i += 256) v += partials[(long)i * 3 + k];
-    tot[k] = block_sum(v, sh);
-  }
+  snwv::sum_partials(partials, n_partials, sh, tot);
   if (threadIdx.x == 0) {
     const double n = (double)n_total;
     const float mse_c = coarse != nullptr ? (float)(tot[0] / n) : 0.0f, mse_f = fine != nullptr ? (float)(tot[1] / n) : 0.0f;
@@ -229,7 +207,7 @@ __global__ void __launch_bounds__(256)
 smooth_kernel(const float* __restrict__ d, const float* __restrict__ I, long n_pix, int H, int W, int C, double inv_nx, double inv_ny,
               float* __restrict__ g_d, float* __restrict__ g_I, double* __restrict__ partials) {
   __shared__ double sh[4];
-  double acc_x = 0.0, acc_y = 0.0;
+  double acc[2] = {0.0, 0.0};                      // the x edges, the y edges
   for (long pix = (long)blockIdx.x * blockDim.x + threadIdx.x; pix < n_pix; pix += (long)gridDim.x * blockDim.x) {
     const int x = (int)(pix % W), y = (int)((pix / W) % H);
     // the four edges of this pixel: right, left, down, up.  `first`: this pixel is A of the edge
@@ -244,8 +222,8 @@ smooth_kernel(const float* __restrict__ d, const float* __restrict__ I, long n_p
       double e, w;
       edge(d, I, first ? pix : other[k], first ? other[k] : pix, C, e, w);
       const double inv = k < 2 ? inv_nx : inv_ny;
-      if (k == 0) acc_x += fabs(e) * w;
-      if (k == 2) acc_y += fabs(e) * w;
+      if (k == 0) acc[0] += fabs(e) * w;
+      if (k == 2) acc[1] += fabs(e) * w;
       gd += (first ? 1.0 : -1.0) * sgn(e) * w * inv;
       coef[k] = -fabs(e) * w * inv / (double)C;              // x sign(I[this, c] - I[other, c]): the same for A and for B
     }
@@ -260,16 +238,15 @@ smooth_kernel(const float* __restrict__ d, const float* __restrict__ I, long n_p
         g_I[pix * C + c] = (float)g;
       }
   }
-  const double vx = block_sum(acc_x, sh), vy = block_sum(acc_y, sh);
-  if (threadIdx.x == 0) { partials[blockIdx.x * 2] = vx; partials[blockIdx.x * 2 + 1] = vy; }
+  snwv::write_block_partials(acc, sh, partials);
 }
 
 __global__ void __launch_bounds__(256)
 smooth_finish_kernel(const double* __restrict__ partials, int n_partials, double inv_nx, double inv_ny, float* __restrict__ out) {
   __shared__ double sh[4];
-  const bool on = (int)threadIdx.x < n_partials;
-  const double tx = block_sum(on ? partials[threadIdx.x * 2] : 0.0, sh), ty = block_sum(on ? partials[threadIdx.x * 2 + 1] : 0.0, sh);
-  if (threadIdx.x == 0) out[0] = (float)(tx * inv_nx + ty * inv_ny);
+  double tot[2];
+  snwv::sum_partials(partials, n_partials, sh, tot);
+  if (threadIdx.x == 0) out[0] = (float)(tot[0] * inv_nx + tot[1] * inv_ny);
 }
 
 static Taps make_taps(int window) {                          // gaussian(window, sigma 1.5), normalised to sum 1
@@ -285,10 +262,7 @@ static Taps make_taps(int window) {                          // gaussian(window,
   return t;
 }
 
-static long flat_blocks(long n) {
-  long blocks = (n + 255) / 256;
-  return blocks < 1 ? 1 : (blocks > FLAT_BLOCKS ? FLAT_BLOCKS : blocks);
-}
+static long flat_blocks(long n) { return (long)snh::stride_grid_min1(n, FLAT_BLOCKS); }
 static long tiles_of(int n) { return ((long)n + TILE - 1) / TILE; }
 
 }  // namespace snp
@@ -310,7 +284,7 @@ extern "C" int sn_patch_loss_launch(const float* coarse, const float* fine, cons
   const long n = (long)B * H * W * C, blocks = sn_patch_loss_blocks_impl(B, H, W, C, use_ssim);
   double* partials = reinterpret_cast<double*>(workspace);
   const bool grads = (g_coarse != nullptr && coarse != nullptr) || (g_fine != nullptr && fine != nullptr);
-  const unsigned grad_blocks = grads ? (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256) : 1u;
+  const unsigned grad_blocks = grads ? snh::stride_grid(n, 4096) : 1u;
   if (use_ssim) {
     const int r = window / 2;
     const Taps taps = make_taps(window);

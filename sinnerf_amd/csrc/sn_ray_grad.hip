@@ -23,6 +23,7 @@
 // Arithmetic is fp32 whatever the layout of g_acts (fp32 rows, bf16 rows, or the (hi, lo) pairs of the bf16x3 state).
 #include "sn_device.h"
 #include "sn_launch.h"
+#include "sn_wave.h"
 
 namespace snrg {
 
@@ -223,11 +224,7 @@ ray_grad_points_kernel(const float* __restrict__ w1, const float* __restrict__ w
   }
 }
 
-SN_DEV double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+using snwv::wave_sum;
 
 // g_o = sum_s g_xyz, g_d = sum_s (z g_xyz + g_dirvec): lane l adds samples l, l + 64, ... in order, then the butterfly
 __global__ void __launch_bounds__(256)
@@ -268,8 +265,8 @@ extern "C" int sn_ray_grads_launch(const float* w1, const float* w5, const float
   const long n_points = n_rays * (long)n_samples;
   const long tiles = (n_points + PTS_WG - 1) / PTS_WG;
   const unsigned grid = snh::persistent_grid(tiles);
-  const long ray_blocks = (n_rays + 3) / 4;
-  if (ray_blocks > 0x7fffffffL) return SN_E_TOOLARGE;
+  dim3 rays_grid;
+  if (const int refused = snh::ray_grid(n_rays, &rays_grid)) return refused;
   constexpr size_t lds = LDS_FLOATS * sizeof(float);
   float* scratch = reinterpret_cast<float*>(workspace);
   const char* G = reinterpret_cast<const char*>(g_acts);
@@ -285,8 +282,7 @@ extern "C" int sn_ray_grads_launch(const float* w1, const float* w5, const float
 #undef SN_RG
   int err = (int)hipGetLastError();
   if (err) return err;
-  hipLaunchKernelGGL(ray_grad_reduce_kernel, dim3((unsigned)ray_blocks), dim3(256), 0, stream, scratch, n_rays, n_samples,
-                     g_rays);
+  hipLaunchKernelGGL(ray_grad_reduce_kernel, rays_grid, dim3(256), 0, stream, scratch, n_rays, n_samples, g_rays);
   return (int)hipGetLastError();
 }
 
@@ -450,9 +446,8 @@ extern "C" int sn_point_grads_launch(const float* w1, const float* w5, int layou
 extern "C" int sn_point_grads_wsum_launch(const float* g_xyz, const float* weights, long n_rays, int n_samples, float* g_sum,
                                           hipStream_t stream) {
   if (n_rays <= 0) return 0;
-  const long ray_blocks = (n_rays + 3) / 4;
-  if (ray_blocks > 0x7fffffffL) return SN_E_TOOLARGE;
-  hipLaunchKernelGGL(snrg::point_grad_wsum_kernel, dim3((unsigned)ray_blocks), dim3(256), 0, stream, g_xyz, weights, n_rays,
-                     n_samples, g_sum);
+  dim3 rays_grid;
+  if (const int refused = snh::ray_grid(n_rays, &rays_grid)) return refused;
+  hipLaunchKernelGGL(snrg::point_grad_wsum_kernel, rays_grid, dim3(256), 0, stream, g_xyz, weights, n_rays, n_samples, g_sum);
   return (int)hipGetLastError();
 }

@@ -10,27 +10,16 @@
 //     A_k = sum_j w_j |m_k - m_j| = m_k (W_<k - W_>k) - (M_<k - M_>k)       dist = sum_k w_k A_k + ...       d dist / d w_k = 2 A_k + (2/3) w_k d_k
 // -- two wave scans.  The layout is the compositor's (sn_render.hip): lane l owns the C consecutive samples [l C, (l + 1) C).  All
 // arithmetic is fp64 on the fp32 inputs, in-lane running sums and cross-lane scans in a fixed order, ONE rounding to fp32 where a value
-// leaves.  Reductions over the rays as in sn_patch_loss.hip: per-block partials in double, re-reduced in index order by a second
+// leaves.  Reductions over the rays with the helpers of sn_wave.h: per-block partials in double, re-reduced in index order by a second
 // launch -- no atomics, the same bits on every call.
 #include "sn_device.h"
 #include "sn_launch.h"
+#include "sn_wave.h"
 
 namespace snq {
 
-// private copies of the wave primitives of sn_render.hip (that translation unit stays as it is)
-SN_DEV double wave_incl_scan_add(double v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double o = __shfl_up(v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-SN_DEV double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+using snwv::wave_incl_scan_add;
+using snwv::wave_sum;
 
 constexpr int N_SUMS = 3;                        // per-block partial record: sum dist, sum ent, rays with the mask set
 
@@ -111,6 +100,8 @@ ray_reg_kernel(const float* __restrict__ weights, const float* __restrict__ z_va
       reinterpret_cast<float2*>(per_ray)[ray] = o;
     }
   }
+  // not snwv::write_block_partials: each wave holds ONE finished value per sum (its ray's), so the four are combined behind a single
+  // barrier, left to right as block_sum does it, instead of a butterfly and two barriers per sum
   if (lane == 0) { sh[wv][0] = r_dist; sh[wv][1] = r_ent; sh[wv][2] = r_mask; }
   __syncthreads();
   if (threadIdx.x < N_SUMS) {
@@ -119,26 +110,14 @@ ray_reg_kernel(const float* __restrict__ weights, const float* __restrict__ z_va
   }
 }
 
-// one block: the partial records summed in index order (thread t takes the records t, t + 256, ...; then the fixed tree of the block)
+// one block: the partial records summed in index order (snwv::sum_partials)
 __global__ void __launch_bounds__(256)
 ray_reg_finish_kernel(const double* __restrict__ partials, long n_partials, long n_rays, float w_dist, float w_ent,
                       float* __restrict__ out) {
-  __shared__ double sh[4][N_SUMS];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  double v[N_SUMS] = {0.0, 0.0, 0.0};
-  for (long i = threadIdx.x; i < n_partials; i += 256)
-#pragma unroll
-    for (int k = 0; k < N_SUMS; ++k) v[k] += partials[i * N_SUMS + k];
-#pragma unroll
-  for (int k = 0; k < N_SUMS; ++k) {
-    v[k] = wave_sum(v[k]);
-    if (lane == 0) sh[wv][k] = v[k];
-  }
-  __syncthreads();
+  __shared__ double sh[4];
+  double t[N_SUMS];
+  snwv::sum_partials(partials, n_partials, sh, t);
   if (threadIdx.x == 0) {
-    double t[N_SUMS];
-#pragma unroll
-    for (int k = 0; k < N_SUMS; ++k) t[k] = ((sh[0][k] + sh[1][k]) + sh[2][k]) + sh[3][k];
     const double n = (double)n_rays, md = t[0] / n, me = t[1] / n;
     out[0] = (float)md;
     out[1] = (float)me;
@@ -147,12 +126,10 @@ ray_reg_finish_kernel(const double* __restrict__ partials, long n_partials, long
   }
 }
 
-static long blocks_of(long n_rays) { return n_rays > 0 ? (n_rays + 3) / 4 : 0; }
-
 }  // namespace snq
 
 extern "C" long sn_ray_regularizers_workspace_bytes_impl(long n_rays) {
-  const long blocks = snq::blocks_of(n_rays);
+  const long blocks = snh::ray_blocks(n_rays);
   return (blocks < 1 ? 1 : blocks) * (long)(snq::N_SUMS * sizeof(double));
 }
 
@@ -161,20 +138,15 @@ extern "C" int sn_ray_regularizers_launch(const float* weights, const float* z_v
                                           void* workspace, float* out, hipStream_t stream) {
   using namespace snq;
   if (n_rays <= 0) return (int)hipMemsetAsync(out, 0, 4 * sizeof(float), stream);
-  const int C = (n_samples + 63) / 64;
-  if (C < 1 || C > 16) return SN_E_BADSHAPE;
-  const long blocks = blocks_of(n_rays);
-  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
+  const int C = snh::samples_per_lane(n_samples);
+  if (!C) return SN_E_BADSHAPE;
+  dim3 grid, block(256);
+  if (const int refused = snh::ray_grid(n_rays, &grid)) return refused;
   double* partials = reinterpret_cast<double*>(workspace);
-  dim3 grid((unsigned)blocks), block(256);
-#define SN_RR(CC)                                                                                                      \
-  case CC:                                                                                                             \
-    hipLaunchKernelGGL((ray_reg_kernel<CC>), grid, block, 0, stream, weights, z_vals, rays, n_rays, n_samples, w_dist, \
-                       w_ent, ent_threshold, g_weights, per_ray, partials);                                            \
-    break;
-  switch (C) { SN_RR(1) SN_RR(2) SN_RR(3) SN_RR(4) SN_RR(5) SN_RR(6) SN_RR(7) SN_RR(8) SN_RR(9) SN_RR(10) SN_RR(11) SN_RR(12)
-               SN_RR(13) SN_RR(14) SN_RR(15) SN_RR(16) }
-#undef SN_RR
-  hipLaunchKernelGGL(ray_reg_finish_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, n_rays, w_dist, w_ent, out);
+  snh::for_samples_per_lane(C, [&](auto c) {
+    hipLaunchKernelGGL((ray_reg_kernel<decltype(c)::value>), grid, block, 0, stream, weights, z_vals, rays, n_rays, n_samples, w_dist,
+                       w_ent, ent_threshold, g_weights, per_ray, partials);
+  });
+  hipLaunchKernelGGL(ray_reg_finish_kernel, dim3(1), dim3(256), 0, stream, partials, (long)grid.x, n_rays, w_dist, w_ent, out);
   return (int)hipGetLastError();
 }

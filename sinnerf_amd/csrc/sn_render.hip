@@ -13,6 +13,7 @@
 // same (fp64 scan, one rounding), which also makes the result independent of the scan tree.
 #include "sn_device.h"
 #include "sn_launch.h"
+#include "sn_wave.h"
 
 namespace snr {
 
@@ -51,28 +52,10 @@ sample_coarse_kernel(const float* __restrict__ rays, long n_rays, int S, int use
   }
 }
 
-// ---- wave primitives -----------------------------------------------------------------------------
-SN_DEV double wave_incl_scan_mul(double v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double o = __shfl_up(v, off, 64);
-    if (lane >= off) v *= o;
-  }
-  return v;
-}
-SN_DEV double wave_incl_scan_add(double v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double o = __shfl_up(v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-SN_DEV double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+// ---- wave primitives (the scans and the butterfly: sn_wave.h) -----------------------------------------
+using snwv::wave_incl_scan_add;
+using snwv::wave_incl_scan_mul;
+using snwv::wave_sum;
 
 SN_DEV void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -423,9 +406,7 @@ extern "C" int sn_sample_coarse_launch(const float* rays, long n_rays, int n_sam
   if (n_rays <= 0) return 0;
   if (perturb > 0.0f && perturb_rand == nullptr) return SN_E_MISSING_RNG;
   const long total = n_rays * (long)n_samples;
-  long blocks = (total + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(snr::sample_coarse_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, rays, n_rays, n_samples,
+  hipLaunchKernelGGL(snr::sample_coarse_kernel, dim3(snh::stride_grid(total, 4096)), dim3(256), 0, stream, rays, n_rays, n_samples,
                      use_disp, perturb, perturb_rand, z_out);
   return (int)hipGetLastError();
 }
@@ -436,21 +417,17 @@ extern "C" int sn_composite_forward_launch(const float* raw, int has_rgb, const 
                                            hipStream_t stream) {
   using namespace snr;
   if (n_rays <= 0) return 0;
-  const int C = (n_samples + 63) / 64;
-  if (C < 1 || C > 16) return SN_E_UNSUPPORTED;
-  const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
-  dim3 grid((unsigned)blocks), block(256);
-#define SN_CL(CC)                                                                                                \
-  case CC:                                                                                                       \
-    if (has_rgb) hipLaunchKernelGGL((composite_fwd_kernel<CC, true>), grid, block, 0, stream, raw, z_vals, rays, noise, \
-                                    noise_std, n_rays, n_samples, white_back, rgb, depth, weights);              \
-    else hipLaunchKernelGGL((composite_fwd_kernel<CC, false>), grid, block, 0, stream, raw, z_vals, rays, noise,  \
-                            noise_std, n_rays, n_samples, white_back, rgb, depth, weights);                      \
-    break;
-  switch (C) { SN_CL(1) SN_CL(2) SN_CL(3) SN_CL(4) SN_CL(5) SN_CL(6) SN_CL(7) SN_CL(8) SN_CL(9) SN_CL(10) SN_CL(11) SN_CL(12)
-               SN_CL(13) SN_CL(14) SN_CL(15) SN_CL(16) }
-#undef SN_CL
+  const int C = snh::samples_per_lane(n_samples);
+  if (!C) return SN_E_UNSUPPORTED;
+  dim3 grid, block(256);
+  if (const int refused = snh::ray_grid(n_rays, &grid)) return refused;
+  snh::for_samples_per_lane(C, [&](auto c) {
+    constexpr int CC = decltype(c)::value;
+    if (has_rgb) hipLaunchKernelGGL((composite_fwd_kernel<CC, true>), grid, block, 0, stream, raw, z_vals, rays, noise, noise_std, n_rays,
+                                    n_samples, white_back, rgb, depth, weights);
+    else hipLaunchKernelGGL((composite_fwd_kernel<CC, false>), grid, block, 0, stream, raw, z_vals, rays, noise, noise_std, n_rays,
+                            n_samples, white_back, rgb, depth, weights);
+  });
   return (int)hipGetLastError();
 }
 
@@ -460,19 +437,14 @@ extern "C" int sn_composite_backward_launch(const float* raw, const float* z_val
                                             hipStream_t stream) {
   using namespace snr;
   if (n_rays <= 0) return 0;
-  const int C = (n_samples + 63) / 64;
-  if (C < 1 || C > 16) return SN_E_UNSUPPORTED;
-  const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
-  dim3 grid((unsigned)blocks), block(256);
-#define SN_CB(CC)                                                                                                \
-  case CC:                                                                                                       \
-    hipLaunchKernelGGL((composite_bwd_kernel<CC>), grid, block, 0, stream, raw, z_vals, rays, noise, noise_std, n_rays, \
-                       n_samples, white_back, g_rgb, g_depth, g_w, g_raw);                                       \
-    break;
-  switch (C) { SN_CB(1) SN_CB(2) SN_CB(3) SN_CB(4) SN_CB(5) SN_CB(6) SN_CB(7) SN_CB(8) SN_CB(9) SN_CB(10) SN_CB(11) SN_CB(12)
-               SN_CB(13) SN_CB(14) SN_CB(15) SN_CB(16) }
-#undef SN_CB
+  const int C = snh::samples_per_lane(n_samples);
+  if (!C) return SN_E_UNSUPPORTED;
+  dim3 grid, block(256);
+  if (const int refused = snh::ray_grid(n_rays, &grid)) return refused;
+  snh::for_samples_per_lane(C, [&](auto c) {
+    hipLaunchKernelGGL((composite_bwd_kernel<decltype(c)::value>), grid, block, 0, stream, raw, z_vals, rays, noise, noise_std, n_rays,
+                       n_samples, white_back, g_rgb, g_depth, g_w, g_raw);
+  });
   return (int)hipGetLastError();
 }
 
@@ -483,19 +455,14 @@ extern "C" int sn_composite_backward_rays_launch(const float* raw, const float* 
                                                  float* g_rays, hipStream_t stream) {
   using namespace snr;
   if (n_rays <= 0) return 0;
-  const int C = (n_samples + 63) / 64;
-  if (C < 1 || C > 16) return SN_E_UNSUPPORTED;
-  const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
-  dim3 grid((unsigned)blocks), block(256);
-#define SN_CBR(CC)                                                                                               \
-  case CC:                                                                                                       \
-    hipLaunchKernelGGL((composite_bwd_rays_kernel<CC>), grid, block, 0, stream, raw, z_vals, rays, noise, noise_std, n_rays, \
-                       n_samples, white_back, g_rgb, g_depth, g_w, g_raw, g_rays);                               \
-    break;
-  switch (C) { SN_CBR(1) SN_CBR(2) SN_CBR(3) SN_CBR(4) SN_CBR(5) SN_CBR(6) SN_CBR(7) SN_CBR(8) SN_CBR(9) SN_CBR(10) SN_CBR(11)
-               SN_CBR(12) SN_CBR(13) SN_CBR(14) SN_CBR(15) SN_CBR(16) }
-#undef SN_CBR
+  const int C = snh::samples_per_lane(n_samples);
+  if (!C) return SN_E_UNSUPPORTED;
+  dim3 grid, block(256);
+  if (const int refused = snh::ray_grid(n_rays, &grid)) return refused;
+  snh::for_samples_per_lane(C, [&](auto c) {
+    hipLaunchKernelGGL((composite_bwd_rays_kernel<decltype(c)::value>), grid, block, 0, stream, raw, z_vals, rays, noise, noise_std,
+                       n_rays, n_samples, white_back, g_rgb, g_depth, g_w, g_raw, g_rays);
+  });
   return (int)hipGetLastError();
 }
 
@@ -504,11 +471,11 @@ extern "C" int sn_sample_pdf_launch(const float* z_vals, const float* weights, c
                                     hipStream_t stream) {
   if (n_rays <= 0) return 0;
   if (n_samples < 3 || n_importance < 1) return SN_E_BADSHAPE;
-  const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
+  dim3 grid;
+  if (const int refused = snh::ray_grid(n_rays, &grid)) return refused;
   const size_t lds = 4 * (size_t)(2 * (n_samples - 1) + 2 * (n_samples + n_importance)) * sizeof(float);
   if (lds > 64 * 1024) return SN_E_UNSUPPORTED;
-  hipLaunchKernelGGL(snr::sample_pdf_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, stream, z_vals, weights, u,
+  hipLaunchKernelGGL(snr::sample_pdf_kernel<true>, grid, dim3(256), lds, stream, z_vals, weights, u,
                      n_rays, n_samples, n_importance, 1e-5f /* render_rays calls sample_pdf with its default eps */, z_fine, z_merged);
   return (int)hipGetLastError();
 }
@@ -519,11 +486,11 @@ extern "C" int sn_sample_pdf_bins_launch(const float* bins, const float* weights
   if (n_rays <= 0) return 0;
   if (n_bins < 1 || n_importance < 1) return SN_E_BADSHAPE;
   const int S = n_bins + 2;
-  const long blocks = (n_rays + 3) / 4;
-  if (blocks > 0x7fffffffL) return SN_E_TOOLARGE;
+  dim3 grid;
+  if (const int refused = snh::ray_grid(n_rays, &grid)) return refused;
   const size_t lds = 4 * (size_t)(2 * (S - 1) + S + n_importance) * sizeof(float);
   if (lds > 64 * 1024) return SN_E_UNSUPPORTED;
-  hipLaunchKernelGGL(snr::sample_pdf_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, stream, bins, weights, u,
+  hipLaunchKernelGGL(snr::sample_pdf_kernel<false>, grid, dim3(256), lds, stream, bins, weights, u,
                      n_rays, S, n_importance, eps, samples, (float*)nullptr);
   return (int)hipGetLastError();
 }

@@ -12,6 +12,7 @@
 // or reads a matrix on the host.
 #include "sn_device.h"
 #include "sn_launch.h"
+#include "sn_wave.h"
 
 namespace snw {
 
@@ -150,8 +151,7 @@ select_count_kernel(const unsigned char* __restrict__ mask, long n, int* __restr
 #pragma unroll
   for (int k = 0; k < 8; ++k)
     if (base + k < n) c += mask[base + k] != 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = snwv::wave_sum(c);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) sums[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
@@ -166,12 +166,7 @@ select_scan_kernel(const int* __restrict__ sums, long n_blocks, int* __restrict_
   for (long tile = 0; tile < n_blocks; tile += 256) {
     const long b = tile + threadIdx.x;
     const int v = b < n_blocks ? sums[b] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
+    const int incl = snwv::wave_incl_scan_add(v, lane);
     __syncthreads();                              // the previous tile's sh has been read
     if (lane == 63) sh[wave] = incl;
     __syncthreads();
@@ -236,7 +231,7 @@ extern "C" int sn_forward_warp_launch(const float* ref_depth, const float* data,
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + WS_HEAD);
   const long n_keys = mode == 0 ? (n + 1) / 2 : n;                   // mode 0 uses the first 4 n bytes as 32-bit keys
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(warp_prepare_kernel, dim3(blocks > 1024u ? 1024u : blocks), dim3(256), 0, stream, ref_proj, src_proj, M, keys,
+  hipLaunchKernelGGL(warp_prepare_kernel, dim3(snh::stride_grid(n, 1024)), dim3(256), 0, stream, ref_proj, src_proj, M, keys,
                      n_keys);
   hipLaunchKernelGGL(warp_scatter_kernel, dim3(blocks), dim3(256), 0, stream, ref_depth, M, H, W, eps, mode, keys);
   hipLaunchKernelGGL(warp_resolve_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, ref_depth,

@@ -27,7 +27,7 @@ from . import _lib
 def _workspace(device):
     # ~10 KB of per-block partial sums, allocated per call from torch's caching allocator (stream-ordered: two streams
     # computing losses concurrently never share it)
-    return torch.empty(_lib.lib.sn_render_loss_workspace_bytes(), dtype=torch.uint8, device=device)
+    return _lib.workspace(_lib.lib.sn_render_loss_workspace_bytes(), "sn_render_loss_workspace_bytes", device)
 
 
 def _prep(t, n, width, name):
@@ -178,10 +178,7 @@ class _PatchLossFn(torch.autograd.Function):
         g_f = torch.empty_like(f) if (f is not None and fine.requires_grad) else None
         out = torch.empty(4, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            nbytes = _lib.lib.sn_patch_loss_workspace_bytes(B, H, W, C, int(use_ssim))
-            if nbytes < 0:
-                _lib.check(nbytes, "sn_patch_loss_workspace_bytes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(_lib.lib.sn_patch_loss_workspace_bytes(B, H, W, C, int(use_ssim)), "sn_patch_loss_workspace_bytes", dev)
             _lib.check(_lib.lib.sn_patch_loss(_lib.ptr(c), _lib.ptr(f), _lib.ptr(t), B, H, W, C, int(use_ssim), int(window),
                                               float(w_mse), float(w_ssim), _lib.ptr(g_c), _lib.ptr(g_f), _lib.ptr(ws), _lib.ptr(out),
                                               _lib.stream_ptr()), "sn_patch_loss")
@@ -214,7 +211,7 @@ class _DepthSmoothnessFn(torch.autograd.Function):
         g_i = torch.empty_like(im) if image.requires_grad else None
         out = torch.empty(1, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            ws = torch.empty(_lib.lib.sn_depth_smoothness_workspace_bytes(), dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(_lib.lib.sn_depth_smoothness_workspace_bytes(), "sn_depth_smoothness_workspace_bytes", dev)
             _lib.check(_lib.lib.sn_depth_smoothness(_lib.ptr(d), _lib.ptr(im), B, H, W, C, _lib.ptr(g_d), _lib.ptr(g_i), _lib.ptr(ws),
                                                     _lib.ptr(out), _lib.stream_ptr()), "sn_depth_smoothness")
         ctx.save_for_backward(*[g for g in (g_d, g_i) if g is not None])

@@ -43,7 +43,7 @@ class _GetRaysFn(torch.autograd.Function):
         H, W, focal, (x0, y0, sx, sy, pw, ph) = ctx.args
         g_rays = g_rays.contiguous().float()
         dev = g_rays.device
-        ws = torch.empty(int(_lib.lib.sn_generate_rays_backward_workspace_bytes()), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(_lib.lib.sn_generate_rays_backward_workspace_bytes(), "sn_generate_rays_backward_workspace_bytes", dev)
         g_c2w = torch.empty((3, 4), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib.sn_generate_rays_backward(_lib.ptr(g_rays), H, W, focal, x0, y0, sx, sy, pw, ph, _lib.ptr(ws),
@@ -85,7 +85,7 @@ class _GetRaysCamFn(torch.autograd.Function):
         c2w, = ctx.saved_tensors
         g_rays = g_rays.contiguous().float()
         dev = g_rays.device
-        ws = torch.empty(int(_lib.lib.sn_generate_rays_backward_workspace_bytes()), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(_lib.lib.sn_generate_rays_backward_workspace_bytes(), "sn_generate_rays_backward_workspace_bytes", dev)
         g_c2w = torch.empty((3, 4), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib.sn_generate_rays_cam_backward(_lib.ptr(g_rays), _lib.ptr(c2w), *_camera_args(H, W, cam), *win,
@@ -121,7 +121,7 @@ class _GetRaysDevFn(torch.autograd.Function):
         ndc = ndc_near is not None
         g_rays = g_rays.contiguous().float()
         dev = g_rays.device
-        ws = torch.empty(int(_lib.lib.sn_camera_backward_workspace_bytes()), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(_lib.lib.sn_camera_backward_workspace_bytes(), "sn_camera_backward_workspace_bytes", dev)
         g_c2w = torch.empty((3, 4), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         g_intr = torch.empty((4,), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         with torch.cuda.device(dev):
@@ -262,7 +262,7 @@ class _NdcRaysDevFn(torch.autograd.Function):
         H, W, near = ctx.args
         rays, focal = ctx.saved_tensors
         g_out = g_out.contiguous().float()
-        ws = torch.empty(int(_lib.lib.sn_camera_backward_workspace_bytes()), dtype=torch.uint8, device=rays.device)
+        ws = _lib.workspace(_lib.lib.sn_camera_backward_workspace_bytes(), "sn_camera_backward_workspace_bytes", rays.device)
         g_in, g_focal = torch.empty_like(rays), torch.empty_like(focal)
         with torch.cuda.device(rays.device):
             _lib.check(_lib.lib.sn_ndc_rays_dev_backward(_lib.ptr(rays), _lib.ptr(g_out), rays.shape[0], H, W, _lib.ptr(focal), near,

@@ -54,7 +54,7 @@ class _RayRegFn(torch.autograd.Function):
             if n == 0:                              # empty batch: the entry's own answer for n_rays <= 0, without its null pointers
                 out.zero_()
             else:
-                ws = torch.empty(_lib.lib.sn_ray_regularizers_workspace_bytes(n), dtype=torch.uint8, device=dev)
+                ws = _lib.workspace(_lib.lib.sn_ray_regularizers_workspace_bytes(n), "sn_ray_regularizers_workspace_bytes", dev)
                 _lib.check(_lib.lib.sn_ray_regularizers(_lib.ptr(w), _lib.ptr(z), _lib.ptr(r), n, s, float(w_dist), float(w_ent),
                                                         float(ent_threshold), _lib.ptr(g_w), _lib.ptr(per_ray), _lib.ptr(ws),
                                                         _lib.ptr(out), _lib.stream_ptr()), "sn_ray_regularizers")

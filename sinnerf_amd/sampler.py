@@ -56,9 +56,7 @@ def valid_windows(mask, stride_x, stride_y, pw, ph, nx=None, ny=None):
     dev = mask.device
     valid = torch.empty((max(ny, 0), max(nx, 0)), dtype=torch.uint8, device=dev)
     n_valid = torch.empty((), dtype=torch.int32, device=dev)
-    nbytes = int(_lib.lib.sn_valid_windows_workspace_bytes(H, nx))
-    _lib.check(min(nbytes, 0), "sn_valid_windows_workspace_bytes")
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(_lib.lib.sn_valid_windows_workspace_bytes(H, nx), "sn_valid_windows_workspace_bytes", dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib.sn_valid_windows(_lib.ptr(mask), H, W, int(stride_x), int(stride_y), int(pw), int(ph), nx, ny,
                                              _lib.ptr(valid), _lib.ptr(n_valid), _lib.ptr(ws), _lib.stream_ptr()), "sn_valid_windows")

@@ -90,9 +90,7 @@ def _warp(data, ref_depth, ref_proj, src_proj, mode, eps, window, want_new=True,
     new_depth = torch.empty((n_out,), dtype=torch.float32, device=dev) if want_depth else None
     mask = torch.empty((n_out,), dtype=torch.uint8, device=dev) if want_mask else None
     winner = torch.empty((n_out,), dtype=torch.int32, device=dev) if want_winner else None
-    nbytes = int(_lib.lib.sn_forward_warp_workspace_bytes(H, W))
-    _lib.check(min(nbytes, 0), "sn_forward_warp_workspace_bytes")
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(_lib.lib.sn_forward_warp_workspace_bytes(H, W), "sn_forward_warp_workspace_bytes", dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib.sn_forward_warp(_lib.ptr(ref_depth), _lib.ptr(data), H, W, C, _lib.ptr(ref_proj), _lib.ptr(src_proj),
                                             float(eps), mode, x0, y0, sx, sy, ow, oh, _lib.ptr(new), _lib.ptr(new_depth),
@@ -168,9 +166,7 @@ def select_landed(mask, u):
     n, m, dev = mask.numel(), u.numel(), mask.device
     idx = torch.empty((m,), dtype=torch.int32, device=dev)
     n_landed = torch.empty((), dtype=torch.int32, device=dev)
-    nbytes = int(_lib.lib.sn_select_landed_workspace_bytes(n))
-    _lib.check(min(nbytes, 0), "sn_select_landed_workspace_bytes")
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(_lib.lib.sn_select_landed_workspace_bytes(n), "sn_select_landed_workspace_bytes", dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib.sn_select_landed(_lib.ptr(mask), n, _lib.ptr(u), m, _lib.ptr(idx), _lib.ptr(n_landed), _lib.ptr(ws),
                                              _lib.stream_ptr()), "sn_select_landed")

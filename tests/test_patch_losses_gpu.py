@@ -79,8 +79,9 @@ def compare(tag, pairs):
         assert np.isfinite(err) and err <= bar, (tag, name, err, e32, bar)
 
 
+# 2 x 192 x 192: 288 tiles = partial records, more than one pass of the 256 threads that re-reduce them (SSIM_SHAPES: 1 to 20 records)
 @pytest.mark.parametrize("family", ["uniform", "near"])
-@pytest.mark.parametrize("shape", SSIM_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", SSIM_SHAPES + [(2, 192, 192, 3)], ids=lambda s: "x".join(map(str, s)))
 def test_l2_ssim_kernel_against_fp64(shape, family):
     coarse, fine, target = patches(shape, family, seed=sum(shape))
     out, g_c, g_f = run_patch_loss(coarse, fine, target, 1)
@@ -132,7 +133,8 @@ def smooth_inputs(shape, seed, constant_block=False):
     return idepth, image
 
 
-@pytest.mark.parametrize("shape,block", [(s, False) for s in SMOOTH_SHAPES] + [((2, 13, 17, 3), True)],
+# 257 x 256 pixels: all 256 partial records of the capped grid, each block more than one stride (SMOOTH_SHAPES: 1 to 16 records)
+@pytest.mark.parametrize("shape,block", [(s, False) for s in SMOOTH_SHAPES] + [((2, 13, 17, 3), True), ((1, 257, 256, 3), False)],
                          ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else ("const" if v else "rand"))
 def test_depth_smoothness_kernel_against_fp64(shape, block):
     idepth, image = smooth_inputs(shape, 11 + sum(shape), block)

@@ -23,7 +23,8 @@ from tests import probe_nets as PN                                              
 from tests import ray_reg_oracle as RO                                                       # noqa: E402
 from tests.test_parity_gpu import dev, embeddings, make_model                                # noqa: E402
 
-SHAPES = [(1, 1), (3, 2), (5, 63), (5, 64), (5, 65), (7, 128), (4, 192), (257, 130), (3, 1023), (2, 1024)]
+# n rays = ceil(n / 4) partial records for the finisher: one, 65, exactly one pass of its 256 threads (1024 rays), a second pass (1027)
+SHAPES = [(1, 1), (3, 2), (5, 63), (5, 64), (5, 65), (7, 128), (4, 192), (257, 130), (3, 1023), (2, 1024), (1024, 2), (1027, 65)]
 WEIGHTS = [(1.0, 0.0), (0.0, 1.0), (0.7, 0.3)]
 BADARG, BADSHAPE = -1, -5
 t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev())
