@@ -520,6 +520,45 @@ long sn_ray_regularizers_workspace_bytes(long n_rays);
 int sn_ray_regularizers(const float* weights, const float* z_vals, const float* rays, long n_rays, int n_samples, float w_dist,
                         float w_ent, float ent_threshold, float* g_weights, float* per_ray, void* workspace, float* out, void* stream);
 
+/* ---- the unseen-view reprojection loss, forward + gradients in two launches (additive within ABI 5): the INVERSE warp of a render into
+ * the reference camera -- the view-synthesis loss of SfMLearner / MonoDepth2 with an occlusion test against the reference depth, and a
+ * free-space term on rendered surfaces in front of what the reference camera saw.  All pointers are DEVICE pointers, ref_proj included.
+ *   rays (n, 8): o = rays[:, 0:3], d = rays[:, 3:6], in WORLD space (not NDC); depth (n): the rendered depth t along each ray;
+ *   rgb (n, C) channel-last, C in 1..4; opacity (n) or NULL; ref_image (H, W, C) channel-last, ref_depth (H, W);
+ *   ref_proj[16]: fp64, row-major, the [K E[:3]; 0 0 0 1] matrix of the reference camera (as sn_forward_warp takes it).
+ *   Integer pixel coordinates are sample positions (sn_forward_warp un-projects source pixel (x, y) the same way).
+ * All in fp64 on the fp32 inputs; every mask is a constant for the gradient.  Per pixel i:
+ *   X = o + t d;  q = P[:3,:3] X + P[:3,3];  z = q2, u = q0 / z, v = q1 / z;
+ *   G (geometrically valid): t finite and t > 0;  z >= z_min;  opacity NULL or opacity_i > opacity_threshold;  0 <= u <= W - 1 and
+ *     0 <= v <= H - 1;  the four corner depths all > 0 (a zero depth is background).  Every comparison is false for NaN.
+ *   x0 = min(floor(u), W - 2), y0 = min(floor(v), H - 2), fx = u - x0, fy = v - y0 (so u = W - 1 is inside, with fx = 1);
+ *   bilinear samples with s00 = s[y0, x0], s10 = s[y0, x0 + 1], s01 = s[y0 + 1, x0], s11 = s[y0 + 1, x0 + 1]:
+ *     s = (1 - fy)((1 - fx) s00 + fx s10) + fy((1 - fx) s01 + fx s11);  D from ref_depth, c_c from ref_image;
+ *   r = (z - D) / D;  V (visible) = G and |r| <= occ_tol;
+ *   photo_i = (1/C) sum_c sqrt((rgb_ic - c_c)^2 + charb_eps^2);  free_i = max(0, -r - occ_tol);  front_i = free_i > 0;
+ *   n_vis = sum V, n_geo = sum G, n_front = sum front;
+ *   photo = n_vis ? sum_V photo_i / n_vis : 0;  free = n_geo ? sum_G free_i / n_geo : 0;  total = w_photo photo + w_free free;
+ *   out[6] = photo, free, total, n_vis, n_geo, n_front.
+ * Gradients of `total`, through the sampling coordinates (the spatial-transformer derivative):
+ *   a = P[:3,:3] d;  z_t = a2, u_t = (a0 - u a2) / z, v_t = (a1 - v a2) / z;
+ *   slopes ds/du = (1 - fy)(s10 - s00) + fy (s11 - s01), ds/dv = (1 - fx)(s01 - s00) + fx (s11 - s10);
+ *   s_ic = (rgb_ic - c_c) / sqrt((rgb_ic - c_c)^2 + charb_eps^2);
+ *   g_rgb_ic = w_photo V_i s_ic / (n_vis C);
+ *   g_depth_i = -(w_photo V_i / (n_vis C)) sum_c s_ic (dc_c/du u_t + dc_c/dv v_t) + (w_free G_i front_i / n_geo) (-r_t),
+ *   r_t = a2 / D - z (dD/du u_t + dD/dv v_t) / D^2.
+ *   g_depth (n), g_rgb (n, C): WRITTEN, not accumulated, exactly 0 wherever the mask is off (no NaN leaks from an invalid pixel).
+ *   per_pixel (n, 2) = (V ? photo_i : 0, G ? free_i : 0).  flags (n) uint8: bit 0 = G, bit 1 = V, bit 2 = front.
+ *   Any of g_depth, g_rgb, per_pixel, flags may be NULL.  The rays, the reference frame and ref_proj receive no gradient.
+ *   workspace: the bytes the query returns for n, DEVICE scratch.  One rounding to fp32 per output, sums in a fixed order without
+ *   atomics: two calls give the same bits.  No host read-back, no allocation: capturable.
+ * SN_E_BADARG: a null required pointer; H < 2 or W < 2; C outside 1..4.  SN_E_TOOLARGE: n or H W C >= 2^31.
+ * n <= 0 launches nothing, sets out to zeros on the stream and returns 0.                                                          */
+long sn_reproject_loss_workspace_bytes(long n);
+int sn_reproject_loss(const float* rays, const float* depth, const float* rgb, const float* opacity, long n, int C,
+                      const float* ref_image, const float* ref_depth, int H, int W, const double* ref_proj, float occ_tol,
+                      float charb_eps, float z_min, float opacity_threshold, float w_photo, float w_free, float* g_depth, float* g_rgb,
+                      float* per_pixel, unsigned char* flags, void* workspace, float* out, void* stream);
+
 /* ---- the forward warp of the reference view and its depth into the unseen view (additive within ABI 5): project_with_depth +
  * forward_warp of datasets/blender_ray_patch_1image_rot3d.py:103-150 (called per training sample, :481-484),
  * blender_ray_patch_1image_proj.py:93-138 (with depth_mask, :135-137), llff_ray_patch_1image_proj.py:117-166 (painter's loop :161-165)

@@ -11,8 +11,9 @@ from .warp import (extrinsics_from_c2w, forward_warp, forward_warp_proj, rotate_
                    unseen_view_batch, unseen_view_full)
 from .sampler import OneImageSampler, gather_windows, valid_windows   # noqa: F401
 from .regularizers import distortion_loss, ray_entropy_loss, ray_regularizers   # noqa: F401
+from .reprojection import reprojection_loss   # noqa: F401
 
 __all__ = ["Embedding", "NeRF", "render_rays", "sample_pdf", "eval_points", "forward_warp", "forward_warp_proj",
            "extrinsics_from_c2w", "rotate_3d", "select_landed", "unseen_view_batch", "unseen_view_full", "OneImageSampler",
            "valid_windows", "gather_windows", "density_gradients", "ray_density_gradients",
-           "render_normals", "ray_regularizers", "distortion_loss", "ray_entropy_loss"]
+           "render_normals", "ray_regularizers", "distortion_loss", "ray_entropy_loss", "reprojection_loss"]

@@ -73,6 +73,9 @@ SIGNATURES = {
     "sn_depth_smoothness": (_int, [c_fp, c_fp, _int, _int, _int, _int, c_fp, c_fp, c_vp, c_fp, c_vp]),
     "sn_ray_regularizers_workspace_bytes": (_long, [_long]),
     "sn_ray_regularizers": (_int, [c_fp, c_fp, c_fp, _long, _int, _float, _float, _float, c_fp, c_fp, c_vp, c_fp, c_vp]),
+    "sn_reproject_loss_workspace_bytes": (_long, [_long]),
+    "sn_reproject_loss": (_int, [c_fp, c_fp, c_fp, c_fp, _long, _int, c_fp, c_fp, _int, _int, c_vp, _float, _float, _float, _float, _float,
+                                 _float, c_fp, c_fp, c_fp, c_vp, c_vp, c_fp, c_vp]),
     "sn_forward_warp_workspace_bytes": (_long, [_int, _int]),
     "sn_forward_warp": (_int, [c_fp, c_fp, _int, _int, _int, c_vp, c_vp, _double, _int, _int, _int, _int, _int, _int, _int, c_fp, c_fp,
                                c_vp, c_vp, c_vp, c_vp]),

@@ -432,6 +432,24 @@ int sn_ray_regularizers(const float* weights, const float* z_vals, const float* 
                                     workspace, out, (hipStream_t)stream);
 }
 
+// ---- the unseen-view reprojection loss (sn_reproject.hip): every refusal below returns before a launch
+long sn_reproject_loss_workspace_bytes(long n) {
+  if (n >= (1l << 31)) return SN_E_TOOLARGE;
+  return sn_reproject_loss_workspace_bytes_impl(n);
+}
+
+int sn_reproject_loss(const float* rays, const float* depth, const float* rgb, const float* opacity, long n, int C,
+                      const float* ref_image, const float* ref_depth, int H, int W, const double* ref_proj, float occ_tol,
+                      float charb_eps, float z_min, float opacity_threshold, float w_photo, float w_free, float* g_depth, float* g_rgb,
+                      float* per_pixel, unsigned char* flags, void* workspace, float* out, void* stream) {
+  if (!rays || !depth || !rgb || !ref_image || !ref_depth || !ref_proj || !workspace || !out) return SN_E_BADARG;
+  if (H < 2 || W < 2 || C < 1 || C > 4) return SN_E_BADARG;
+  if (n >= (1l << 31) || (long)H * W * C >= (1l << 31)) return SN_E_TOOLARGE;
+  return sn_reproject_loss_launch(rays, depth, rgb, opacity, n, C, ref_image, ref_depth, H, W, ref_proj, occ_tol, charb_eps, z_min,
+                                  opacity_threshold, w_photo, w_free, g_depth, g_rgb, per_pixel, flags, workspace, out,
+                                  (hipStream_t)stream);
+}
+
 // ---- the unseen-view forward warp (sn_warp.hip): every refusal below returns before a launch
 namespace {
 int check_frame(int H, int W) {

@@ -241,6 +241,12 @@ long sn_ray_regularizers_workspace_bytes_impl(long n_rays);
 int sn_ray_regularizers_launch(const float* weights, const float* z_vals, const float* rays, long n_rays, int n_samples, float w_dist,
                                float w_ent, float ent_threshold, float* g_weights, float* per_ray, void* workspace, float* out,
                                hipStream_t stream);
+// the unseen-view reprojection loss: the inverse warp of a render into the reference camera (sn_reproject.hip)
+long sn_reproject_loss_workspace_bytes_impl(long n);
+int sn_reproject_loss_launch(const float* rays, const float* depth, const float* rgb, const float* opacity, long n, int C,
+                             const float* ref_image, const float* ref_depth, int H, int W, const double* ref_proj, float occ_tol,
+                             float charb_eps, float z_min, float opacity_threshold, float w_photo, float w_free, float* g_depth,
+                             float* g_rgb, float* per_pixel, unsigned char* flags, void* workspace, float* out, hipStream_t stream);
 // the unseen-view forward warp and the draw among the landed pixels (sn_warp.hip)
 long sn_forward_warp_workspace_bytes_impl(int H, int W);
 int sn_forward_warp_launch(const float* ref_depth, const float* data, int H, int W, int C, const double* ref_proj, const double* src_proj,

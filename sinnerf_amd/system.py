@@ -24,6 +24,7 @@ from .optim import FlatAdam, FlatOptimizer, FlatSGD, GradualWarmupScheduler, get
 from .parallel import all_reduce_mean_grads, broadcast_parameters
 from .losses import inverse_depth_smoothness_loss, loss_dict, psnr, render_loss      # noqa: F401  (psnr re-exported: metrics.py:14-15)
 from .regularizers import ray_regularizers
+from .reprojection import reprojection_loss
 from .rendering import render_rays
 
 DEFAULT_HPARAMS = dict(N_samples=64, N_importance=64, use_disp=False, perturb=1.0, noise_std=1.0, chunk=32 * 1024,
@@ -41,7 +42,11 @@ DEFAULT_HPARAMS = dict(N_samples=64, N_importance=64, use_disp=False, perturb=1.
                        warmup_epochs=0,
                        # regularisers on the compositing weights of the unseen-view render (sinnerf_amd/regularizers.py; not in the
                        # reference): the distortion loss of Mip-NeRF 360 and the ray entropy of InfoNeRF.  The defaults add no term
-                       distortion_weight=0.0, entropy_weight=0.0, entropy_threshold=0.1)
+                       distortion_weight=0.0, entropy_weight=0.0, entropy_threshold=0.1,
+                       # the reprojection of the unseen-view render into the reference camera (sinnerf_amd/reprojection.py; not in the
+                       # reference): the photometric term over the pixels the reference camera sees and the free-space term on rendered
+                       # surfaces in front of its depth.  The defaults add no term
+                       reproj_weight=0.0, freespace_weight=0.0, reproj_occlusion_tol=0.05, reproj_opacity_threshold=0.5)
 
 
 
@@ -251,6 +256,9 @@ class SinNeRFSystem(nn.Module):
         Not in the reference: with ``distortion_weight > 0`` or ``entropy_weight > 0``, ``ray_regularizers`` on the compositing weights
         of the unseen-view render -- the fine pass, and the coarse pass when its weights carry a gradient.  ``results_side`` then holds
         the depths of its passes under the private keys ``_z_vals_fine`` / ``_z_vals_coarse`` (``_training_step_patches`` puts them there).
+        With ``reproj_weight > 0`` or ``freespace_weight > 0``, ``reprojection_loss`` of the unseen-view render against the reference view
+        -- the batch keys ``ref_view`` (H, W, 3), ``ref_depth`` (H, W), ``ref_proj`` (4, 4) fp64, which ``train_step_sampled`` adds from its
+        sampler -- on ``(rgb_fine, depth_fine)``, and on the coarse pair when it carries a gradient; ``rays_side`` must be world-space rays.
         """
         hp = self.hparams
         wd = hp.depth_weight
@@ -319,6 +327,26 @@ class SinNeRFSystem(nn.Module):
                 l_ent = st["entropy"] if l_ent is None else l_ent + st["entropy"]
             loss = loss + l_reg
             log["train/loss_distortion"], log["train/loss_ray_entropy"] = l_dist, l_ent
+        if hp.reproj_weight > 0 or hp.freespace_weight > 0:
+            missing = [k for k in ("ref_view", "ref_depth", "ref_proj") if k not in batch]
+            if missing:
+                raise RuntimeError(f"reproj_weight / freespace_weight > 0 need the reference view in the batch: {missing} missing "
+                                   "(ref_view (H, W, 3), ref_depth (H, W), ref_proj (4, 4) fp64; train_step_sampled adds them)")
+            rays_side = batch["rays_side"].reshape(-1, 8)
+            passes = ["fine" if "rgb_fine" in results_side else "coarse"]
+            if passes[0] == "fine" and results_side["depth_coarse"].requires_grad:
+                passes.append("coarse")
+            l_rep = l_photo = l_free = None
+            for k in passes:
+                term, st = reprojection_loss(rays_side, results_side["depth_" + k], results_side["rgb_" + k], batch["ref_view"],
+                                             batch["ref_depth"], batch["ref_proj"], opacity=results_side["opacity_" + k].detach().sum(-1),
+                                             w_photo=hp.reproj_weight, w_free=hp.freespace_weight, occ_tol=hp.reproj_occlusion_tol,
+                                             opacity_threshold=hp.reproj_opacity_threshold)
+                l_rep = term if l_rep is None else l_rep + term
+                l_photo = st["photo"] if l_photo is None else l_photo + st["photo"]
+                l_free = st["free"] if l_free is None else l_free + st["free"]
+            loss = loss + l_rep
+            log["train/loss_reproj"], log["train/loss_freespace"] = l_photo, l_free
         l_side = self.side_loss(results_side, batch)
         if l_side is not None:
             loss = loss + l_side
@@ -474,7 +502,8 @@ class SinNeRFSystem(nn.Module):
                self._flat.flat.data_ptr() if self._flat is not None else None,
                hp.N_samples, hp.N_importance, hp.use_disp, hp.perturb, hp.noise_std, hp.chunk, hp.depth_weight,
                hp.compute_dtype, self.white_back, self.training, hp.patch_loss, hp.depth_smooth_weight, hp.proj_weight,
-               hp.dataset_name, hp.distortion_weight, hp.entropy_weight, hp.entropy_threshold)
+               hp.dataset_name, hp.distortion_weight, hp.entropy_weight, hp.entropy_threshold, hp.reproj_weight, hp.freespace_weight,
+               hp.reproj_occlusion_tol, hp.reproj_opacity_threshold)
         cache = self.__dict__.setdefault("_step_graphs", {})
         hit = cache.get(key)
         if hit is None:
@@ -504,7 +533,9 @@ class SinNeRFSystem(nn.Module):
     def train_step_sampled(self, sampler, graph=False):
         """``train_step`` on a batch drawn on the device: ``batch = sampler.draw()`` (``sinnerf_amd.sampler.OneImageSampler``: what the
         reference's DataLoader workers build per sample on the CPU), then zero -> forward -> loss -> backward and the optimiser's
-        exchange step.  No part of the step waits for the host.
+        exchange step.  No part of the step waits for the host.  With ``reproj_weight`` or ``freespace_weight`` positive the batch also
+        carries the sampler's ``ref_view``, ``ref_depth`` and ``ref_proj`` (``_sampled_batch``); a sampler whose camera maps its rays to
+        NDC is then refused.
 
         ``graph=True``: the draw is INSIDE the captured region, in front of the step; every replay draws fresh randoms (torch's
         generators advance their offset per replay; a sampler's own generator is registered with the graph).  Warm-up and invalidation as
@@ -514,10 +545,21 @@ class SinNeRFSystem(nn.Module):
         if graph:
             out = self._graphed_sampled_step(sampler)
         else:
-            batch = sampler.draw()
+            batch = self._sampled_batch(sampler)
             out = dict(self._zero_forward_backward(batch), batch=batch)
         self.optimizer.step()
         return out
+
+    def _sampled_batch(self, sampler):
+        """``sampler.draw()``; with the reprojection terms on, the reference view the sampler holds joins the batch (``ref_view``,
+        ``ref_depth``, ``ref_proj``: the tensors themselves, no copy)"""
+        hp = self.hparams
+        if not (hp.reproj_weight > 0 or hp.freespace_weight > 0):
+            return sampler.draw()
+        if sampler.cam.get("ndc_near") is not None:
+            raise RuntimeError("reproj_weight / freespace_weight > 0: the sampler's camera maps its rays to NDC (ndc_near set); the "
+                               "reprojection needs world-space rays")
+        return dict(sampler.draw(), ref_view=sampler.ref_view, ref_depth=sampler.ref_depth, ref_proj=sampler.ref_proj)
 
     def _graphed_sampled_step(self, sampler):
         hp = self.hparams
@@ -526,7 +568,8 @@ class SinNeRFSystem(nn.Module):
                self._flat.flat.data_ptr() if self._flat is not None else None,
                hp.N_samples, hp.N_importance, hp.use_disp, hp.perturb, hp.noise_std, hp.chunk, hp.depth_weight,
                hp.compute_dtype, self.white_back, self.training, hp.patch_loss, hp.depth_smooth_weight, hp.proj_weight,
-               hp.dataset_name, hp.distortion_weight, hp.entropy_weight, hp.entropy_threshold)
+               hp.dataset_name, hp.distortion_weight, hp.entropy_weight, hp.entropy_threshold, hp.reproj_weight, hp.freespace_weight,
+               hp.reproj_occlusion_tol, hp.reproj_opacity_threshold)
         cache = self.__dict__.setdefault("_step_graphs", {})     # shared with _graphed_step: dropped with it when the buffers move
         hit = cache.get(key)
         if hit is None:
@@ -537,7 +580,7 @@ class SinNeRFSystem(nn.Module):
             side.wait_stream(cur)
             with torch.cuda.stream(side):        # the warm-up of _graphed_step, the draw included
                 for _ in range(2):
-                    self._zero_forward_backward(sampler.draw())
+                    self._zero_forward_backward(self._sampled_batch(sampler))
             cur.wait_stream(side)
             for m in self.models:                # the re-pack of the weight blobs belongs to the captured step (_graphed_step)
                 m.invalidate_packed()
@@ -545,7 +588,7 @@ class SinNeRFSystem(nn.Module):
             if sampler.generator is not None:
                 g.register_generator_state(sampler.generator)
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                batch = sampler.draw()
+                batch = self._sampled_batch(sampler)
                 out = dict(self._zero_forward_backward(batch), batch=batch)
             hit = cache[key] = (g, sampler, out)                 # the sampler is kept: its id stays its own while the entry lives
         g, _, out = hit
